@@ -8,13 +8,21 @@ configs[1] (C2: 1 Mi x 1514-B IPv4/TCP frames, 1 flow); at N>1 GPUs = configs[3]
 (C4: 16 Mi x 1514-B frames over 1024 flows sharded by index across 8 GPUs, i.e.
 2 Mi frames per GPU, rank r owning global frames [r*2Mi, (r+1)*2Mi)): weak scaling,
 no collective on the data path (the frames shard by index and nothing is exchanged,
-SURVEY §8e).  Every rank sha256-gates its own shard against the committed oracle
-digest.  torch.distributed over gloo (host-side, no RCCL) carries only the start/stop
+SURVEY §8e).  With --full every rank sha256-gates its own shard against the committed
+oracle digest.  torch.distributed over gloo (host-side, no RCCL) carries only the start/stop
 barriers, the reductions of the timing and the gathered gates; the aggregate is timed
 over one common barrier-to-barrier window.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--frames N]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--frames N] [--dump-outputs DIR]
+  python bench.py --full ...       (the same, with everything listed under "--full" below)
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: it generates the resident batches, warms up,
+times the K steps and prints the line (metric, value, unit, ms_per_step, the kernel's roofline).
+--dump-outputs DIR then also writes the records of the last timed step (the generator is seeded: the
+same arguments give the same frames in every run, so two builds can be compared record for record).
+--full adds the correctness gate, the same-run ceilings, the secondary workloads, the end-to-end legs
+and the CPU baseline described below.
 
 Without torchrun, --gpus N > 1 spawns the N ranks itself (spawn start method, before
 anything touches a GPU in the parent); rank r uses device r % device_count, so on a
@@ -22,8 +30,8 @@ box with fewer GPUs than ranks the same flow runs as a rehearsal (ranks share a 
 "ranks_per_device" in the line).
 
 Rank 0 prints ONE JSON line: metric = wire Gbit/s = 8*sum(14+tot_len)/t plus
-Mframes/s, the roofline of the kernel, the correctness gate (full-batch sha256 against
-tests/golden/full_digests.json), and at N=1 the secondary workloads (C3, C5, a packed
+Mframes/s and the roofline of the kernel; with --full also the correctness gate (full-batch sha256
+against tests/golden/full_digests.json), and at N=1 the secondary workloads (C3, C5, a packed
 C3 capture through pn_classify_indexed, the TX checksum fill at frame_off 2 and 14),
 the CPU baseline and the pinned-host end-to-end rates.
 """
@@ -60,6 +68,13 @@ def parse():
     ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 4, 5],
                     help="workload (default: C2 at one GPU, C4 = BASELINE configs[3] at N>1)")
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU (default: 1 Mi; C4: 2 Mi)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the correctness gate against the oracle and the committed "
+                         "digests, the same-run ceilings, the secondary workloads, the end-to-end legs and the CPU "
+                         "baseline (the options below choose among them); without it: set up, warm up, time the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last timed step to DIR/records.npy "
+                         "(float64, one column per record field; at N>1 each rank its records_rank<r>.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="no end-to-end legs (host ring in, records out)")
     ap.add_argument("--e2e", action="store_true",
@@ -72,7 +87,12 @@ def parse():
     ap.add_argument("--batches", type=int, default=4,
                     help="distinct resident batches the steps rotate over (defeats reuse of a fixed slice of "
                          "the 256 MiB memory-side cache across launches)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and (args.e2e or args.stream_ceiling_only):
+        ap.error("--e2e and --stream-ceiling-only choose among the legs of --full: add --full")
+    return args
 
 
 def log(*a):
@@ -1065,6 +1085,33 @@ def peak_rss_mib():
     return round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024, 1)
 
 
+DUMP_ROWS = 1 << 20  # records written by --dump-outputs over all ranks: 6 float64 each = 48 MiB
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path, res, n, rank, world):
+    """--dump-outputs: what the timed path left in its caller's record buffer after the last timed step, one row
+    per frame and one float64 column per field of the 16-B record (conn_id, seq, payload_off, payload_len, flags,
+    tcp_fold: every field is exact in a float64).  At most DUMP_ROWS rows over all ranks: of a larger output a
+    fixed, seeded sample of rows in ascending order, whose indices go beside it."""
+    import pollnet_amd as pa
+
+    os.makedirs(path, exist_ok=True)
+    name = "records" if world == 1 else f"records_rank{rank}"
+    rec = res.cpu().numpy().view(pa.RESULT_DTYPE)[:n]
+    rows = max(1, DUMP_ROWS // world)
+    if n > rows:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, rows, replace=False))
+        np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+        rec = rec[idx]
+    cols = np.empty((len(rec), len(pa.RESULT_DTYPE.names)), dtype=np.float64)
+    for c, f in enumerate(pa.RESULT_DTYPE.names):
+        cols[:, c] = rec[f]
+    np.save(os.path.join(path, name + ".npy"), cols)
+    return {"dir": path, "file": name + ".npy", "rows": len(rec), "of": n, "columns": list(pa.RESULT_DTYPE.names),
+            "batch": "the resident batch of the last timed step"}
+
+
 # ----------------------------------------------------------------------------- ranks
 def _json_stdout():
     """stdout carries the one JSON line only: fd 1 is pointed at stderr for everything else
@@ -1138,7 +1185,7 @@ def run_rank(rank, world, local_rank, args):
             pa.gen_frames(params, n, STRIDE, FRAME_OFF, first_index=firsts[b], threads=gen_threads, out=dst)
         wires.append(pa.wire_bytes(dst, STRIDE, FRAME_OFF, n))
         frames_b.append(torch.from_numpy(dst.reshape(-1)).to(f"cuda:{dev}"))
-        if b == 0:
+        if b == 0 and args.full:
             # N=1 keeps batch 0 on the host (CPU baseline, e2e legs); N>1 ranks keep only the rows
             # the in-run oracle check reads
             if world == 1:
@@ -1157,40 +1204,42 @@ def run_rank(rank, world, local_rank, args):
     # the workload's invariants; each batch whose global frame range has a committed digest (made by the
     # oracle: C2/C3/C5 [0, 1 Mi), each of C4's 8 shards) must hash to it; the first 4096 records of
     # batch 0 are re-checked against the oracle in this run
-    inv_ok = True
-    got0 = None
-    sha_ok, sha_gated = True, 0
-    for b in range(R):
-        ctx.classify(frames_b[b], STRIDE, FRAME_OFF, n, res, stream)
-        torch.cuda.synchronize()
-        rec = res.view(n, 16)
-        flags = rec[:, 12].to(torch.int32) | (rec[:, 13].to(torch.int32) << 8)
-        if cfg in (2, 4):  # every frame: valid IP header, a known flow, 54-B headers + 1460-B payload
-            off_len = rec[:, 8:12].contiguous().view(torch.int32).flatten()
-            inv_ok &= bool(torch.all((flags & 0x5) == 0x5)) and bool(torch.all(off_len == (54 | (1460 << 16))))
-        else:
-            inv_ok &= bool(torch.all((flags & 0x4000) == 0))
-        host_rec = res.cpu().numpy()
-        gd = golden_digest(cfg, firsts[b], n)
-        if gd is not None:
-            sha_gated += 1
-            sha_ok &= hashlib.sha256(host_rec.tobytes()).hexdigest() == gd["records_sha256"]
-        if b == 0:
-            got0 = host_rec
-    from oracle import pyoracle as orc
+    gate = {"checked": False, "note": "the gate against the oracle and the committed digests runs with --full"}
+    verified, fully_gated, got0 = False, False, None
+    if args.full:
+        inv_ok = True
+        sha_ok, sha_gated = True, 0
+        for b in range(R):
+            ctx.classify(frames_b[b], STRIDE, FRAME_OFF, n, res, stream)
+            torch.cuda.synchronize()
+            rec = res.view(n, 16)
+            flags = rec[:, 12].to(torch.int32) | (rec[:, 13].to(torch.int32) << 8)
+            if cfg in (2, 4):  # every frame: valid IP header, a known flow, 54-B headers + 1460-B payload
+                off_len = rec[:, 8:12].contiguous().view(torch.int32).flatten()
+                inv_ok &= bool(torch.all((flags & 0x5) == 0x5)) and bool(torch.all(off_len == (54 | (1460 << 16))))
+            else:
+                inv_ok &= bool(torch.all((flags & 0x4000) == 0))
+            host_rec = res.cpu().numpy()
+            gd = golden_digest(cfg, firsts[b], n)
+            if gd is not None:
+                sha_gated += 1
+                sha_ok &= hashlib.sha256(host_rec.tobytes()).hexdigest() == gd["records_sha256"]
+            if b == 0:
+                got0 = host_rec
+        from oracle import pyoracle as orc
 
-    k = min(n, 4096)
-    exp = orc.classify_batch(slots, STRIDE, FRAME_OFF, k, entries, mask, table.max_conn_cnt, threads=8)
-    gate = {"all_batches_invariants": inv_ok, "batches_sha256_gated": f"{sha_gated}/{R}",
-            # None: no committed digest covers this frame range (e.g. a --frames override)
-            "gated_batches_sha256_match_golden": bool(sha_ok) if sha_gated else None,
-            "batch0_first_4096_vs_oracle": bool(np.array_equal(got0[: k * 16].view(pa.RESULT_DTYPE), exp))}
-    verified = all(v for v in gate.values() if isinstance(v, bool))
-    # without a committed digest for its frames a rank is checked by invariants and 4096 records only:
-    # that is reported as "partial", never as verified
-    fully_gated = sha_gated == R
-    if not verified:
-        log(f"ERROR [rank {rank}]: correctness gate failed: {gate}")
+        k = min(n, 4096)
+        exp = orc.classify_batch(slots, STRIDE, FRAME_OFF, k, entries, mask, table.max_conn_cnt, threads=8)
+        gate = {"all_batches_invariants": inv_ok, "batches_sha256_gated": f"{sha_gated}/{R}",
+                # None: no committed digest covers this frame range (e.g. a --frames override)
+                "gated_batches_sha256_match_golden": bool(sha_ok) if sha_gated else None,
+                "batch0_first_4096_vs_oracle": bool(np.array_equal(got0[: k * 16].view(pa.RESULT_DTYPE), exp))}
+        verified = all(v for v in gate.values() if isinstance(v, bool))
+        # without a committed digest for its frames a rank is checked by invariants and 4096 records only:
+        # that is reported as "partial", never as verified
+        fully_gated = sha_gated == R
+        if not verified:
+            log(f"ERROR [rank {rank}]: correctness gate failed: {gate}")
     setup_s = round(time.perf_counter() - t_rank, 1)
 
     for w in range(args.warmup):
@@ -1215,6 +1264,7 @@ def run_rank(rank, world, local_rank, args):
         shm_barrier = ShmBarrier(dist, rank, world)
     wall_max, own_max = common_window(timed_steps, dist if world > 1 else None, shm_barrier)
     kern_ms = ev0.elapsed_time(ev1) / args.steps
+    dumped = dump_outputs(args.dump_outputs, res, n, rank, world) if args.dump_outputs else None
     gate.update(device_identity(torch, dev))
     gate.update({"kernel_ms": round(kern_ms, 5), "setup_s": setup_s, "peak_rss_mib": peak_rss_mib()})
     step_wire = float(sum(wires[k % R] for k in range(args.steps)))  # this rank's wire bytes over the K steps
@@ -1266,9 +1316,13 @@ def run_rank(rank, world, local_rank, args):
                        "coordination": "gloo (host): setup, max/sum of the timing, gates; the timed window between "
                                        "start/stop barriers" if world > 1 else
                        "single process"},
-            "verified_vs_oracle": (bool(all_verified) if all_gated or not all_verified else "partial"),
+            "full": bool(args.full),
+            # null: not checked in this run (the gate is one of --full's legs)
+            "verified_vs_oracle": None if not args.full else (
+                bool(all_verified) if all_gated or not all_verified else "partial"),
             "correctness_gate": gate if world == 1 else {
-                "every_rank_verified": bool(all_verified), "every_rank_sha256_gated": bool(all_gated),
+                "every_rank_verified": bool(all_verified) if args.full else None,
+                "every_rank_sha256_gated": bool(all_gated) if args.full else None,
                 "distinct_devices": len({g["pci_bus_id"] for g in gates}),
                 "setup_s_max": max(g["setup_s"] for g in gates),
                 "peak_rss_mib_max": max(g["peak_rss_mib"] for g in gates), "ranks": gates},
@@ -1288,7 +1342,9 @@ def run_rank(rank, world, local_rank, args):
         out["e2e_host_ring"] = e2e
     elif rank == 0 and ring_error:
         out["e2e_host_ring"] = {"error": ring_error}
-    if rank == 0 and world == 1:
+    if rank == 0 and dumped is not None:
+        out["dumped_outputs"] = dumped
+    if rank == 0 and world == 1 and args.full:
         out["roofline"]["same_run_ceilings"] = ceilings(torch, ctx, frames_b, n, res, stream,
                                                         stream_only=args.stream_ceiling_only)
     if rank == 0 and world == 1 and not args.no_secondary and cfg == 2 and n == 1 << 20:
@@ -1377,6 +1433,8 @@ def _spawned(rank, world, args, port):
 
 def main():
     args = parse()
+    if not args.full:  # the plain run: the headline alone
+        args.no_secondary = args.no_cpu_baseline = args.no_e2e = True
     if args.e2e:
         args.no_secondary = args.no_cpu_baseline = True
         args.no_e2e = False

@@ -16,7 +16,7 @@ for c in ('c2','c3'):
     print(c, ' '.join(f\"{v}:{r['ms']}\" for v,r in M[c]['variants'].items()))
 "
 echo skip-trace && exit 0
-  python3 bench.py --no-cpu-baseline --no-e2e --no-secondary --steps 50 > $OUT/prof_c2_bench.json 2> $OUT/prof_c2.err || { echo "c2 trace failed"; tail -20 $OUT/prof_c2.err; exit 1; }
+  python3 bench.py --full --no-cpu-baseline --no-e2e --no-secondary --steps 50 > $OUT/prof_c2_bench.json 2> $OUT/prof_c2.err || { echo "c2 trace failed"; tail -20 $OUT/prof_c2.err; exit 1; }
 find $OUT/prof_c2 -name "*kernel_stats.csv" -exec grep -h "rx_classify_kernel" {} \; | cut -c1-200
 python3 -c "import json; L=json.load(open('$OUT/prof_c2_bench.json')); print('line', L['roofline']['kernel_ms_avg'], L['roofline']['frac'])"
 echo r4d-ok

@@ -14,7 +14,7 @@ tail -2 $OUT/ref_client_gpu40.log
 for N in 2 4; do
   PORT=$((20000 + RANDOM % 20000))
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT \
-    bench.py --gpus $N --steps 20 --warmup 3 > $OUT/bench_n${N}_torchrun.json 2> $OUT/bench_n${N}_torchrun.err \
+    bench.py --full --gpus $N --steps 20 --warmup 3 > $OUT/bench_n${N}_torchrun.json 2> $OUT/bench_n${N}_torchrun.err \
     || { echo "n$N failed"; tail -20 $OUT/bench_n${N}_torchrun.err; exit 1; }
   python3 -c "
 import json; L=json.load(open('$OUT/bench_n${N}_torchrun.json')); cg=L['correctness_gate']

@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 PORT=$((20000 + RANDOM % 20000))
 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port $PORT \
-  bench.py --gpus 8 --steps 20 --warmup 3 > $OUT/bench_n8_torchrun.json 2> $OUT/bench_n8_torchrun.err \
+  bench.py --full --gpus 8 --steps 20 --warmup 3 > $OUT/bench_n8_torchrun.json 2> $OUT/bench_n8_torchrun.err \
   || { echo "n8 failed"; tail -30 $OUT/bench_n8_torchrun.err; exit 1; }
 python3 -c "
 import json; L=json.load(open('$OUT/bench_n8_torchrun.json')); cg=L['correctness_gate']

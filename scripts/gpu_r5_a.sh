@@ -16,7 +16,7 @@ step() {  # name, seconds, command...
   return 0
 }
 step tests 420 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread
-step bench 420 python bench.py
+step bench 420 python bench.py --full
 if [ "$2" = tx ]; then
   for off in 14 2; do
     step tx_ab_off$off 300 python scripts/tx_variants.py --frame-off $off --variants 40,50,51,52,41 --rotate 4 --rounds 9

@@ -21,7 +21,7 @@ step service 400 python -u -m pytest tests/test_gpu_links.py tests/test_gpu_serv
 tail -25 $OUT/service.out
 step tests 600 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread -p no:cacheprovider
 tail -3 $OUT/tests.out
-step bench 420 python bench.py
+step bench 420 python bench.py --full
 python3 -c "import json; L=json.load(open('$OUT/bench.out')); print(json.dumps(L['summary'])); print(json.dumps(L['secondary'].get('service_large_post')))"
 # where the host spends a poll (item 2): the sampler (bench/sampler.hpp) over the best GPU leg, the reference's own
 # server and the CPU twin's dispatch, on this box's cores; symbolized here (llvm-symbolizer) into text

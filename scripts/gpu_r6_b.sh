@@ -35,5 +35,5 @@ for f in ("srv_C",):
     for k in ("cpu_rxbatch_512_pipelined_release_path_timed","cpu_rxbatch_512_pipelined_linked_release_path_timed"):
         print(f, k, statistics.median(x[k]["ns_per_frame_dispatch"] for x in t))
 P
-step bench 420 python bench.py
+step bench 420 python bench.py --full
 python3 -c "import json; L=json.load(open('$OUT/bench.out')); print(json.dumps(L['summary']))"

@@ -9,7 +9,7 @@ for c in 2 3 5; do
     || { echo "config $c failed"; tail -5 $OUT/window_c$c.err; exit 1; }
   python -c "import json,sys; d=json.load(open('$OUT/window_c$c.json')); print($c, {k: v['ms_median'] for k, v in d.items() if isinstance(v, dict) and 'algo_tbps' in v})"
 done
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-e2e > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-e2e > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
 python -c "
 import json; d=json.load(open('$OUT/bench.json')); s=d['secondary']
 print('c2', d['roofline']['kernel_ms_avg'], d['roofline']['frac'], 'c3', s['c3']['frac'], 'packed', s['c3']['packed_indexed']['frac'], 'c5', s['c5']['frac'],

@@ -244,7 +244,8 @@ def test_bench_spawns_ranks_itself():
     import sys
 
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--frames", "65536", "--batches", "2", "--no-cpu-baseline", "--no-e2e", "--no-secondary"],
+                        "--frames", "65536", "--batches", "2", "--full", "--no-cpu-baseline", "--no-e2e",
+                        "--no-secondary"],
                        capture_output=True, text=True, timeout=240, env={k: v for k, v in os.environ.items()
                                                                         if k not in ("WORLD_SIZE", "RANK")})
     assert p.returncode == 0, p.stderr[-3000:]
@@ -276,7 +277,7 @@ def test_bench_under_the_drivers_torchrun_command():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--batches", "2", "--no-cpu-baseline", "--no-e2e", "--no-secondary"]
+           "--warmup", "1", "--batches", "2", "--full", "--no-cpu-baseline", "--no-e2e", "--no-secondary"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -371,7 +372,7 @@ def test_device_numa_lookup():
 
 @pytest.mark.gpu
 def test_bench_e2e_host_ring_two_ranks():
-    """`bench.py --gpus 2 --e2e` under the driver's torchrun command on this box's one GPU: the end-to-end leg's
+    """`bench.py --gpus 2 --full --e2e` under the driver's torchrun command on this box's one GPU: the end-to-end leg's
     plumbing (one shared host ring, each rank's C4 shard of 2 Mi frames first-touched on its GPU's NUMA node,
     hipHostRegister-ed and classified in place, records into the ring) with every shard gated: each rank's batches
     hash to its shard's committed digest, and its ring records equal its device-resident records, in both modes.
@@ -386,7 +387,7 @@ def test_bench_e2e_host_ring_two_ranks():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--batches", "2", "--e2e"]
+           "--warmup", "1", "--batches", "2", "--full", "--e2e"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
