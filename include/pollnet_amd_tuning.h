@@ -3,8 +3,8 @@
  *
  * NOT part of the product ABI (include/pollnet_amd.h) and never loaded by the product
  * path: same-run bandwidth ceilings that bench.py reports beside the production kernel,
- * and (unless built with `make TUNING=0`) the A/B variants of the RX and TX kernels that
- * scripts/variants.py / scripts/tx_variants.py time.  Contexts come from pn_open().
+ * and (unless built with `make TUNING=0`) the A/B variants of the TX fill that
+ * scripts/tx_variants.py times.  Contexts come from pn_open().
  */
 #ifndef POLLNET_AMD_TUNING_H
 #define POLLNET_AMD_TUNING_H
@@ -21,8 +21,7 @@ int pn_calib_stream_read(pn_ctx* ctx, const void* src_dev, uint64_t bytes, void*
 /* Ceiling for a slot layout: the first `bytes` (<= 2048) of each of n_slots slots,
  * read with the RX kernel's own load pattern and no arithmetic; store_bytes = 16 / 8
  * also writes that many bytes per slot to sink_dev (n_slots x 16 B) like the RX
- * kernel's records, 0 writes nothing; 16 | G << 8 (G = 1, 4, 16) writes the 16-B records of
- * G consecutive 64-slot groups in one burst per workgroup (write-grouping probe). */
+ * kernel's records, 0 writes nothing. */
 int pn_calib_slot_read(pn_ctx* ctx, const void* src_dev, uint32_t n_slots, uint32_t stride, uint32_t bytes,
                        int store_bytes, void* sink_dev, void* stream);
 /* Ceiling for variable-length frames: slot i's first lens_dev[i] bytes (u32 per slot, device
@@ -65,10 +64,6 @@ int pn_test_doorbell_echo_pipe(const uint32_t* bell_host, uint32_t* echo_host, u
                                uint32_t gap, void* stream);
 
 /* ---- A/B variants (built by default, TUNING=1; ids documented at their definitions) ---- */
-int pn_classify_variant(pn_ctx* ctx, const void* frames_dev, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
-                        void* results_dev, void* stream, int variant);
-int pn_classify_indexed_variant(pn_ctx* ctx, const void* base, const uint64_t* offsets, uint32_t eth_mod16, uint32_t n,
-                                uint32_t avail, void* results_dev, void* stream, int variant);
 int pn_tx_fill_variant(pn_ctx* ctx, void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
                        const uint16_t* lens, int variant, void* stream);
 

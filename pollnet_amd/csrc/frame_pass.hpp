@@ -27,21 +27,19 @@ using Window = Win<4 * kWinChunks>;
 
 constexpr uint32_t kPadUnknown = 0xFFFFFFFFu;
 
-// Timing-only ablations (scripts/variants.py; records are wrong when set):
-// bit0 skip the conn-table probe, bit1 skip the lane reduction, bit2 no tail
-// masks, bit3 no record store.
-enum : int { kAblNoProbe = 1, kAblNoReduce = 2, kAblNoMask = 4, kAblNoStore = 8, kAblStore8 = 16, kAblGlobalStore = 32 };
+// Flags of the frame pass (the ABL parameter of the RX kernel, SABL of the TX fill).  Each keeps the value it
+// was measured under: the kernels' demangled names, which carry them, are keys in profiles/pmc_traffic.json.
+// Timing-only ablations (records are wrong when set), for the same-run ceilings bench.py reports:
+// bit0 skip the conn-table probe, bit1 skip the lane reduction.
+enum : int { kAblNoProbe = 1, kAblNoReduce = 2 };
 // Not an ablation: kExactRange bounds each frame's stream descriptor at its extent rounded
 // up to a dword, so the hardware's per-dword range check zeroes the bytes past the extent
 // and the per-dword tail masks go; a 2-mod-4 extent leaves 2 bytes of the last dword,
 // subtracted on the lane that loaded them.
 enum : int { kExactRange = 64 };
 // kCoopProbe: conn-table lookups that continue past the home slot are finished by the whole
-// wave, 64 entries per round trip (header_phase in rx_kernel.hip).
+// wave, 64 entries per round trip (probe_finish in rx_classify.hpp).
 enum : int { kCoopProbe = 256 };
-// Timing only (tuning library, packed indexed captures): phase 2 streams the wave's frames as ONE
-// contiguous byte range with fully used 1-KiB loads, summed into one garbage total (records wrong).
-enum : int { kAblContigStream = 512 };
 // Not an ablation: a stream load whose whole 1-KiB range lies past the frame's extent (it would
 // return zeros and fetch nothing) is not issued at all -- a wave-uniform branch on the frame's
 // extent.  Mixed-size frames (most end inside the first KiB) skip up to half their load
@@ -57,16 +55,9 @@ enum : int { kSkipWaveGate = 16384 };
 // C5 -3.9 % (0.1660 -> 0.1596 ms; the probe's share over the no-probe ablation 13.6 -> 7.2 us),
 // C3 equal (profiles/r03/probe_group_c{3,5}.json).
 enum : int { kGroupProbe = 32768 };
-// Tuning: kLateProbe issues the home-slot load in phase 1 and finishes the walk after phase 2 (the
-// round trip under the stream loads); kAblNoWalk (timing only) stops every probe at its home slot.
-enum : int { kLateProbe = 4096, kAblNoWalk = 8192 };
-// Timing only (with kAblNoWalk): every lane of a wave loads the same home entry (the first lane's), so the
-// probe instruction touches one line instead of up to 64 — isolates the cost of the scattered probe loads.
-enum : int { kAblUniformProbe = 131072 };
 // kSerialWindow: the window loads as they were until round 3, a branch around each (the compiler waits for
-// each before issuing the next); in the RX kernel (tuning only) also the LDS-pad test's per-lane write to a.n
-// that made every descriptor built from it a waterfall loop.  RX production issues all 8 at once (C3 -3.8 %,
-// C5 -4.3 %, C2 equal); the TX fill keeps the serial form, measured faster there (tx_fill.hpp, kTxStream).
+// each before issuing the next).  The RX kernel issues all 8 at once (C3 -3.8 %, C5 -4.3 %, C2 equal); the TX
+// fill keeps the serial form, measured faster there (tx_fill.hpp, kTxStream).
 enum : int { kSerialWindow = 1 << 20 };
 // With kSkipWaveGate: phase 2 of full-size waves software-pipelined by half batches
 // (stream_phase_pipelined; slot strides up to 2048).  C2 -1.4 %, C3/C5 unchanged (their waves take
@@ -76,12 +67,8 @@ enum : int { kPipeStream = 1 << 21 };
 // Retired probe forms (measured, not adopted; DESIGN §4, profiles/r03/probe_ablation/): 2048 home slot + 3
 // ahead, 65536 probe pipelined into phase 2, 262144 home entries through the scalar cache (code: commit 229bb94);
 // 524288 a run-length hint in the device table's pad word sending long runs straight to the group walk (c3575ae).
-// The production RX configuration.
-// timing only: every wave's records into the first 16 KiB of the output (the stores issued, almost no
-// write-back volume)
-enum : int { kAblSmallStore = 1 << 22 };
-// timing only: the wave's record store issued before its loads (dummy records), none at its end
-enum : int { kAblEarlyStore = 1 << 23 };
+// The other values that are no flag here (4 .. 32, 512, 4096, 8192, 131072, 1 << 22, 1 << 23) were A/B variants of
+// the RX kernel, retired with their results in DESIGN §4, "Retired RX variants".
 // product (pn_set_verify(ctx, 0)): no segment stream and no TCP verdict -- the header lines only, as the
 // reference's release path reads them (Core::checksum is debug-only, Core.h:448-478)
 enum : int { kHeaderOnly = 1 << 24 };
@@ -89,6 +76,7 @@ enum : int { kHeaderOnly = 1 << 24 };
 // scratch, when set) -- the record again and the ack number, destination address, window and destination port --
 // for the post's chain pass (rx_service.hip chain_pass)
 enum : int { kChainAux = 1 << 25 };
+// The production RX configuration.
 constexpr int kProdAbl = kExactRange | kCoopProbe | kGroupProbe | kSkipEmptyLoads | kSkipWaveGate | kPipeStream;
 
 // Header window of lane `lane`'s slot for a strided layout (slot r of the wave at
@@ -131,7 +119,7 @@ __device__ __forceinline__ uint32_t load_window_strided(__amdgpu_buffer_rsrc_t r
     // All 8 loads in flight before the first LDS write: a part that is not needed gets an offset past
     // the descriptor's range (returns zeros, fetches nothing) instead of a branch around its load --
     // with the branches the compiler waited for each load before issuing the next (8 round trips).
-    if constexpr (SERIAL) { // tuning (kSerialWindow): the round-1..3 form, a branch around each load
+    if constexpr (SERIAL) { // kSerialWindow (the TX fill): the round-1..3 form, a branch around each load
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const uint32_t r = 8 * i + (lane >> 3), part = lane & 7;
@@ -256,6 +244,7 @@ __device__ __forceinline__ uint32_t stream_start(uint64_t w) { return 112u - (((
 template <int ABL, int LAUX, int IDX>
 __device__ __forceinline__ void stream_phase(uint32_t stride, const uint8_t* group_ipa, uint64_t my_win, uint32_t n_here,
                                              int lane, int end_rel, uint32_t& t_all, uint32_t& pad) {
+  static_assert(ABL & kExactRange, "every frame's stream descriptor ends at its dword-exact extent");
   // window start of frame fi: strided from the group's first slot, or (indexed) the
   // address its own lane computed, broadcast with two readlanes
   auto frame_win = [&](uint32_t fi) -> const uint8_t* {
@@ -277,14 +266,13 @@ __device__ __forceinline__ void stream_phase(uint32_t stride, const uint8_t* gro
       const uint32_t fi = b0 + j; // wave-uniform
       const int end = __builtin_amdgcn_readlane(end_rel, fi & 63) & ~1; // bit 0 = odd tcp_len, read below
       ends[j] = end;
-      const uint32_t end16 = (ABL & kExactRange) ? ((uint32_t)(end + 3) & ~3u)  // dword-exact extent
-                                                 : ((uint32_t)(end + 15) & ~15u); // 0 for frames past n (end_rel = 0 there)
+      const uint32_t end16 = (uint32_t)(end + 3) & ~3u; // dword-exact extent; 0 for frames past n (end_rel = 0 there)
       const uint8_t* fw = frame_win(fi);
       const int s0 = (int)stream_start((uint64_t)fw);
       s0s[j] = s0;
       const __amdgpu_buffer_rsrc_t rs = frame_rsrc(fw, end16);
       // out-of-range chunks of a buffer load return 0 and fetch nothing
-      if constexpr ((ABL & kSkipEmptyLoads) && (ABL & kExactRange)) {
+      if constexpr (ABL & kSkipEmptyLoads) {
         const u32x4 z = {0u, 0u, 0u, 0u};
         w0s[j] = end16 > (uint32_t)s0 ? __builtin_amdgcn_raw_buffer_load_b128(rs, s0 + lane * 16, 0, LAUX) : z;
         w1s[j] = end16 > (uint32_t)s0 + 1024 ? __builtin_amdgcn_raw_buffer_load_b128(rs, s0 + 1024 + lane * 16, 0, LAUX) : z;
@@ -294,10 +282,11 @@ __device__ __forceinline__ void stream_phase(uint32_t stride, const uint8_t* gro
       }
     }
     __builtin_amdgcn_sched_barrier(0); // keep the whole batch in flight before the first wait
-    auto sel = [](int e, int o) -> uint32_t {
-      if constexpr (ABL & (kAblNoMask | kExactRange)) return 0x10001u;
-      else return tail_sel(e, o);
-    };
+    // Both halves of every dword count: the descriptor's exact range has zeroed what lies past the extent.  The
+    // (extent, offset) arguments are what the per-dword tail masks took before kExactRange; writing the constant at
+    // the call sites instead changes the code of 40 RX and 48 TX kernels (measured when the masks were removed), so
+    // the lambda and its arguments stay until the kernels are next re-measured.
+    auto sel = [](int, int) -> uint32_t { return 0x10001u; };
 #pragma unroll
     for (int j = 0; j < kBatch; ++j) {
       const int end = ends[j], s0 = s0s[j];
@@ -312,15 +301,13 @@ __device__ __forceinline__ void stream_phase(uint32_t stride, const uint8_t* gro
       sum = dot2(w1.y, sel(end, o1 + 4), sum);
       sum = dot2(w1.z, sel(end, o1 + 8), sum);
       sum = dot2(w1.w, sel(end, o1 + 12), sum);
-      if constexpr (ABL & kExactRange) {
-        // end % 4 == 2: the last dword loaded holds the 2 bytes after the extent (its high half)
-        const int q = end - 2 - s0; // wave-uniform
-        if ((end & 2) && q >= 0 && q < 2048) {
-          const u32x4 w = (q < 1024) ? w0 : w1;
-          const int dw = (q >> 2) & 3;
-          const uint32_t d = dw == 0 ? w.x : dw == 1 ? w.y : dw == 2 ? w.z : w.w;
-          if (lane == ((q & 1023) >> 4)) sum -= d >> 16;
-        }
+      // end % 4 == 2: the last dword loaded holds the 2 bytes after the extent (its high half)
+      const int q2 = end - 2 - s0; // wave-uniform
+      if ((end & 2) && q2 >= 0 && q2 < 2048) {
+        const u32x4 w = (q2 < 1024) ? w0 : w1;
+        const int dw = (q2 >> 2) & 3;
+        const uint32_t d = dw == 0 ? w.x : dw == 1 ? w.y : dw == 2 ? w.z : w.w;
+        if (lane == ((q2 & 1023) >> 4)) sum -= d >> 16;
       }
       acc[j] = sum;
       // odd tcp_len: the RFC verdict needs the byte the reference sums past the segment (window

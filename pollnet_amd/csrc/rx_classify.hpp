@@ -1,6 +1,7 @@
 // rx_classify.hpp — the RX classify kernel (device code + launch helpers), shared by the
 // product library (rx_kernel.hip: the production instantiations behind pn_classify /
-// pn_classify_indexed) and the tuning library (rx_tuning.hip: A/B variants, ceilings).
+// pn_classify_indexed; rx_service.hip: the resident service) and the tuning library
+// (rx_tuning.hip: the ablated same-run ceiling).
 // Included by exactly one translation unit per library; everything is internal linkage.
 #pragma once
 
@@ -9,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "../../include/pollnet_amd.h"
 #include "device_common.hpp"
@@ -92,11 +94,13 @@ struct FrameState {
   int end_rel;    // summed extent relative to the window start (even), | 1 when tcp_len is odd; 0 = nothing to stream
   uint32_t pad;   // odd tcp_len: the byte after the segment (kPadUnknown until phase 2 captured it)
   bool trunc;
-  Probe probe; // kLateProbe: the issued probe, finished after phase 2
+  // Unused since the late-probe form was retired ("Retired RX variants").  It stays: removing it changed
+  // the register allocation and scheduling of every kernel, measured at the commit that retired the form.  The next
+  // change that re-measures the kernel takes it out.
+  Probe probe;
 };
 
 // connHashKey (Core.h:167-172) and the load of the home slot `key & tbl_mask` (Core.h:558-559).
-template <int ABL>
 __device__ __forceinline__ Probe probe_issue(uint32_t src_ip, uint32_t src_port, bool live, const KArgs& a) {
   Probe p;
   const uint32_t ip_h = __builtin_bswap32(src_ip);
@@ -106,9 +110,7 @@ __device__ __forceinline__ Probe probe_issue(uint32_t src_ip, uint32_t src_port,
   p.k = PN_EMPTY_KEY;
   p.cid = 0;
   if (live && p.e < a.n_entries) { // the home slot: almost every lookup ends here
-    uint32_t eh = p.e;
-    if constexpr (ABL & kAblUniformProbe) eh = __builtin_amdgcn_readfirstlane(eh); // timing only
-    const u32x4 ent = *reinterpret_cast<const u32x4*>(a.tbl + eh);
+    const u32x4 ent = *reinterpret_cast<const u32x4*>(a.tbl + p.e);
     p.k = ((uint64_t)ent.y << 32) | ent.x;
     p.cid = ent.z;
   }
@@ -116,119 +118,79 @@ __device__ __forceinline__ Probe probe_issue(uint32_t src_ip, uint32_t src_port,
 }
 
 // The rest of findConnEntry's ordered walk (Core.h:560-561) and the conn / TIME_WAIT / miss
-// verdict (Core.h:510).  Every lane of the wave must call it (the cooperative walk ballots).
-template <int ABL>
+// verdict (Core.h:510).  Every lane of the wave must call it (the walk ballots).
 __device__ __forceinline__ void probe_finish(const Probe& p, bool live, const KArgs& a, uint32_t& conn_id, uint32_t& flags) {
   const uint64_t key = p.key;
   uint32_t e = p.e;
   uint64_t k = p.k;
   uint32_t cid = p.cid;
-  if constexpr (ABL & kAblNoWalk) {
-    // timing only: the home slot decides
-  } else if constexpr (ABL & kCoopProbe) {
-    // Lanes whose run continues past the home slot are served one at a time by the whole
-    // wave (all 64 lanes reach here): 64 consecutive entries per round trip, the first with
-    // key >= the lane's key (or the array end) found by a ballot -- the entry the scalar
-    // walk stops at.
-    const uint32_t lane = threadIdx.x;
-    bool srch = live && e < a.n_entries && k < key;
-    if (__ballot(srch) != 0) {
-      // short runs (the common case past the home slot): every searching lane fetches its
-      // next kAhead entries at once -- one round trip for all of them, in parallel
-      constexpr int kAhead = 2;
-      u32x4 nx[kAhead];
+  // Lanes whose run continues past the home slot are served by the whole wave (all 64 lanes
+  // reach here): 64 consecutive entries per round trip, the first with key >= the lane's key
+  // (or the array end) found by a ballot -- the entry the scalar walk stops at.
+  const uint32_t lane = threadIdx.x;
+  bool srch = live && e < a.n_entries && k < key;
+  if (__ballot(srch) != 0) {
+    // short runs (the common case past the home slot): every searching lane fetches its
+    // next kAhead entries at once -- one round trip for all of them, in parallel
+    constexpr int kAhead = 2;
+    u32x4 nx[kAhead];
 #pragma unroll
-      for (int j = 0; j < kAhead; ++j) {
-        nx[j] = u32x4{0u, 0u, 0u, 0u};
-        if (srch && e + 1 + j < a.n_entries) nx[j] = *reinterpret_cast<const u32x4*>(a.tbl + e + 1 + j);
-      }
-      uint32_t step = 0, cid2 = 0;
-      uint64_t k2 = 0;
+    for (int j = 0; j < kAhead; ++j) {
+      nx[j] = u32x4{0u, 0u, 0u, 0u};
+      if (srch && e + 1 + j < a.n_entries) nx[j] = *reinterpret_cast<const u32x4*>(a.tbl + e + 1 + j);
+    }
+    uint32_t step = 0, cid2 = 0;
+    uint64_t k2 = 0;
 #pragma unroll
-      for (int j = kAhead - 1; j >= 0; --j) { // the first entry (in order) that stops the walk
-        const uint64_t kk = ((uint64_t)nx[j].y << 32) | nx[j].x;
-        if (e + 1 + j >= a.n_entries || kk >= key) {
-          step = j + 1;
-          k2 = kk;
-          cid2 = nx[j].z;
-        }
-      }
-      if (srch) {
-        if (step != 0) {
-          e += step;
-          k = k2;
-          cid = cid2;
-          srch = false;
-        } else {
-          e += kAhead; // every fetched key < key: the run goes on
-        }
+    for (int j = kAhead - 1; j >= 0; --j) { // the first entry (in order) that stops the walk
+      const uint64_t kk = ((uint64_t)nx[j].y << 32) | nx[j].x;
+      if (e + 1 + j >= a.n_entries || kk >= key) {
+        step = j + 1;
+        k2 = kk;
+        cid2 = nx[j].z;
       }
     }
-    uint64_t need = __ballot(srch);
-    if constexpr (ABL & kGroupProbe) {
-      while (need != 0) { // wave-uniform
-        // the lanes at the first searching lane's run position: one fetch serves them all
-        const uint32_t e0 = __builtin_amdgcn_readlane(e, (uint32_t)__builtin_ctzll(need));
-        uint64_t group = __ballot(srch && e == e0);
-        for (uint32_t base = e0 + 1; group != 0; base += kWave) {
-          const uint32_t idx = base + lane;
-          u32x4 ent = {0u, 0u, 0u, 0u};
-          if (idx < a.n_entries) ent = *reinterpret_cast<const u32x4*>(a.tbl + idx);
-          const uint64_t kk = ((uint64_t)ent.y << 32) | ent.x;
-          for (uint64_t pend = group; pend != 0; pend &= pend - 1) {
-            const uint32_t L = (uint32_t)__builtin_ctzll(pend);
-            const uint64_t kl = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(key >> 32), L) << 32) |
-                                (uint32_t)__builtin_amdgcn_readlane((uint32_t)key, L);
-            const uint64_t stop = __ballot(idx >= a.n_entries || kk >= kl);
-            if (stop != 0) { // the entry lane L's scalar walk stops at
-              const uint32_t first = (uint32_t)__builtin_ctzll(stop);
-              const uint32_t klo = __builtin_amdgcn_readlane(ent.x, first), khi = __builtin_amdgcn_readlane(ent.y, first);
-              const uint32_t c = __builtin_amdgcn_readlane(ent.z, first);
-              if (lane == L) {
-                e = base + first;
-                k = ((uint64_t)khi << 32) | klo;
-                cid = c;
-                srch = false;
-              }
-              group &= ~(1ull << L);
-            }
-          }
-        }
-        need = __ballot(srch);
+    if (srch) {
+      if (step != 0) {
+        e += step;
+        k = k2;
+        cid = cid2;
+        srch = false;
+      } else {
+        e += kAhead; // every fetched key < key: the run goes on
       }
-    } else {
-      while (need != 0) { // wave-uniform
-        const uint32_t L = (uint32_t)__builtin_ctzll(need);
-        need &= need - 1;
+    }
+  }
+  uint64_t need = __ballot(srch);
+  while (need != 0) { // wave-uniform
+    // the lanes at the first searching lane's run position: one fetch serves them all
+    const uint32_t e0 = __builtin_amdgcn_readlane(e, (uint32_t)__builtin_ctzll(need));
+    uint64_t group = __ballot(srch && e == e0);
+    for (uint32_t base = e0 + 1; group != 0; base += kWave) {
+      const uint32_t idx = base + lane;
+      u32x4 ent = {0u, 0u, 0u, 0u};
+      if (idx < a.n_entries) ent = *reinterpret_cast<const u32x4*>(a.tbl + idx);
+      const uint64_t kk = ((uint64_t)ent.y << 32) | ent.x;
+      for (uint64_t pend = group; pend != 0; pend &= pend - 1) {
+        const uint32_t L = (uint32_t)__builtin_ctzll(pend);
         const uint64_t kl = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(key >> 32), L) << 32) |
                             (uint32_t)__builtin_amdgcn_readlane((uint32_t)key, L); // readlane returns int
-        for (uint32_t base = __builtin_amdgcn_readlane(e, L) + 1;; base += kWave) {
-          const uint32_t idx = base + lane;
-          u32x4 ent = {0u, 0u, 0u, 0u};
-          if (idx < a.n_entries) ent = *reinterpret_cast<const u32x4*>(a.tbl + idx);
-          const uint64_t kk = ((uint64_t)ent.y << 32) | ent.x;
-          const uint64_t stop = __ballot(idx >= a.n_entries || kk >= kl);
-          if (stop != 0) {
-            const uint32_t first = (uint32_t)__builtin_ctzll(stop);
-            const uint32_t klo = __builtin_amdgcn_readlane(ent.x, first), khi = __builtin_amdgcn_readlane(ent.y, first);
-            const uint32_t c = __builtin_amdgcn_readlane(ent.z, first);
-            if (lane == L) {
-              e = base + first;
-              k = ((uint64_t)khi << 32) | klo;
-              cid = c;
-            }
-            break;
+        const uint64_t stop = __ballot(idx >= a.n_entries || kk >= kl);
+        if (stop != 0) { // the entry lane L's scalar walk stops at
+          const uint32_t first = (uint32_t)__builtin_ctzll(stop);
+          const uint32_t klo = __builtin_amdgcn_readlane(ent.x, first), khi = __builtin_amdgcn_readlane(ent.y, first);
+          const uint32_t c = __builtin_amdgcn_readlane(ent.z, first);
+          if (lane == L) {
+            e = base + first;
+            k = ((uint64_t)khi << 32) | klo;
+            cid = c;
+            srch = false;
           }
+          group &= ~(1ull << L);
         }
       }
     }
-  } else {
-    while (live && e < a.n_entries && k < key) {
-      if (++e >= a.n_entries) break;
-      const u32x4 ent = *reinterpret_cast<const u32x4*>(a.tbl + e);
-      k = ((uint64_t)ent.y << 32) | ent.x;
-      cid = ent.z;
-    }
+    need = __ballot(srch);
   }
   if (live && e < a.n_entries && k == key) {
     conn_id = cid;
@@ -284,13 +246,16 @@ __device__ __forceinline__ FrameState header_phase(const Window& h, uint32_t eth
   // (Resolving the probe after phase 2 instead, so the home-slot load overlaps the stream loads,
   // measured no faster: profiles/r02/s3/late_probe_ab.json.)
   st.conn_id = PN_MISS;
-  if constexpr (ABL & kLateProbe) st.probe = probe_issue<ABL>(st.src_ip, src_port, live, a);
-  else if constexpr (!(ABL & kAblNoProbe)) probe_finish<ABL>(probe_issue<ABL>(st.src_ip, src_port, live, a), live, a, st.conn_id, flags);
+  if constexpr (!(ABL & kAblNoProbe)) probe_finish(probe_issue(st.src_ip, src_port, live, a), live, a, st.conn_id, flags);
   st.flags = flags;
   return st;
 }
 
 // ---- phase 3: fold and write the record on the frame's lane ----
+// lds_rec is always nullptr: it belonged to the retired burst-record form ("Retired RX variants").  Like
+// FrameState::probe it stays, with its never-taken branch below: without them all 80 production kernels come out
+// scheduled differently, measured at the commit that retired the form.  The next change that re-measures the kernel
+// takes both out.
 template <int MIS, int ABL, int SAUX>
 __device__ __forceinline__ void finish(const KArgs& a, FrameState st, uint32_t f, const uint8_t* win, bool bad_off,
                                        u32x4* lds_rec, uint32_t cx_ack = 0, uint32_t cx_wport = 0) {
@@ -335,26 +300,16 @@ __device__ __forceinline__ void finish(const KArgs& a, FrameState st, uint32_t f
       aux[2 * f + 1] = u32x4{cx_ack, st.dst_ip, cx_wport, 0u};
     }
   }
-  if (lds_rec) { // grouped launches write the workgroup's records in one burst at its end
+  if (lds_rec) {
     *lds_rec = rec;
-  } else if constexpr (ABL & (kAblNoStore | kAblEarlyStore)) {
-    if (rec.x == 0x7eadbeefu && rec.y == 0x12345678u) *reinterpret_cast<u32x4*>(a.out + f) = rec; // ~never
-  } else if constexpr (ABL & kAblSmallStore) { // timing only: 16 blocks of 64 records, rewritten by every wave
-    const uint32_t blk = __builtin_amdgcn_readfirstlane((f & ~63u) & 0x3C0u);
-    const __amdgpu_buffer_rsrc_t rs = frame_rsrc((const uint8_t*)(a.out + blk), 64 * 16);
-    __builtin_amdgcn_raw_buffer_store_b128(rec, rs, (f & 63u) * 16, 0, SAUX);
-  } else if constexpr (ABL & kAblStore8) { // timing only: half the record bytes
-    reinterpret_cast<uint2*>(a.out)[f] = uint2{rec.x ^ rec.y, rec.z ^ rec.w};
-  } else if constexpr (ABL & kAblGlobalStore) { // the record through a plain global store (SAUX ignored)
-    *reinterpret_cast<u32x4*>(a.out + f) = rec;
-  } else {
-    // one coalesced 1-KiB store per wave; the descriptor covers this wave's 64 records.  The block is the
-    // same on every lane (a wave's frames never cross a 64-frame boundary): readfirstlane makes the
-    // descriptor scalar, where a per-lane one would be a waterfall loop around the store
-    const uint32_t blk = __builtin_amdgcn_readfirstlane(f & ~63u);
-    const __amdgpu_buffer_rsrc_t rs = frame_rsrc((const uint8_t*)(a.out + blk), 64 * 16);
-    __builtin_amdgcn_raw_buffer_store_b128(rec, rs, (f & 63u) * 16, 0, SAUX);
+    return;
   }
+  // one coalesced 1-KiB store per wave; the descriptor covers this wave's 64 records.  The block is the
+  // same on every lane (a wave's frames never cross a 64-frame boundary): readfirstlane makes the
+  // descriptor scalar, where a per-lane one would be a waterfall loop around the store
+  const uint32_t blk = __builtin_amdgcn_readfirstlane(f & ~63u);
+  const __amdgpu_buffer_rsrc_t rs = frame_rsrc((const uint8_t*)(a.out + blk), 64 * 16);
+  __builtin_amdgcn_raw_buffer_store_b128(rec, rs, (f & 63u) * 16, 0, SAUX);
 }
 
 // ---- the kernel: one 64-frame group per 64-thread workgroup ----
@@ -369,7 +324,7 @@ __device__ __forceinline__ void finish(const KArgs& a, FrameState st, uint32_t f
 // Register target: 4 waves/SIMD.  Until round 3 the MIS % 4 == 0 kernels fit 5 (<= 96 VGPRs) and the
 // LDS pad below held them at 4; the grouped probe takes them to 102 VGPRs (104 with the pipelined phase 2), so registers and pad agree.
 template <int MIS, int COOP, int ABL, int LAUX, int SAUX, int IDX, int LWIN>
-__device__ __forceinline__ void classify_group(const KArgs& a, const uint32_t wave_base, const int lane, u32x4* lds_recs) {
+__device__ __forceinline__ void classify_group(const KArgs& a, const uint32_t wave_base, const int lane) {
   if (wave_base >= a.n) return;
   const uint32_t f = wave_base + lane;
   const uint32_t n_here = min(a.fpw, a.n - wave_base);
@@ -377,11 +332,6 @@ __device__ __forceinline__ void classify_group(const KArgs& a, const uint32_t wa
   const uint8_t* wave_slot = a.frames + (uint64_t)wave_base * a.stride;
   // one wave-uniform descriptor over the wave's slots; lanes past n read zeros
   const __amdgpu_buffer_rsrc_t rs = frame_rsrc(wave_slot, n_here * a.stride);
-  if constexpr (ABL & kAblEarlyStore) {
-    const uint32_t blk = __builtin_amdgcn_readfirstlane(f & ~63u);
-    const __amdgpu_buffer_rsrc_t ro = frame_rsrc((const uint8_t*)(a.out + blk), 64 * 16);
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{f, 0u, 0u, 0u}, ro, (f & 63u) * 16, 0, SAUX);
-  }
 
   Window h;
   uint32_t ether_type;
@@ -479,106 +429,69 @@ __device__ __forceinline__ void classify_group(const KArgs& a, const uint32_t wa
       }
     }
   } else {
-    ether_type = load_window_strided<MIS, COOP, LWIN, (ABL & kSerialWindow) != 0>(rs, lane, a.stride, a.ipa_off,
-                                                                                    (uint32_t)(uintptr_t)wave_slot, h);
+    ether_type = load_window_strided<MIS, COOP, LWIN>(rs, lane, a.stride, a.ipa_off, (uint32_t)(uintptr_t)wave_slot, h);
   }
   if constexpr (!IDX) win = wave_slot + (uint64_t)lane * a.stride + a.ipa_off;
   FrameState st = header_phase<MIS, ABL>(h, ether_type, live && !bad_off, stream_start((uint64_t)win), a);
-  if constexpr (IDX && (ABL & kAblContigStream)) {
-    // timing only: [first frame's stream start, last frame's extent end) as one range, 16 x 1 KiB per round
-    const uint64_t w = (uint64_t)win;
-    const uint64_t lo64 = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(w >> 32), 0) << 32) |
-                          (uint32_t)__builtin_amdgcn_readlane((uint32_t)w, 0);
-    const uint32_t last = n_here - 1;
-    const uint64_t hw = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(w >> 32), last) << 32) |
-                        (uint32_t)__builtin_amdgcn_readlane((uint32_t)w, last);
-    const uint64_t lo = (lo64 + stream_start(lo64)) & ~15ull;
-    const uint64_t hi = (hw + (uint32_t)(__builtin_amdgcn_readlane(st.end_rel, last) & ~1) + 15) & ~15ull;
-    const uint32_t len = hi > lo ? (uint32_t)(hi - lo) : 0u;
-    const __amdgpu_buffer_rsrc_t rc = frame_rsrc((const uint8_t*)lo, len);
-    uint32_t sum = 0;
-    for (uint32_t o = 0; o < len; o += 16 * 1024) {
-      u32x4 v[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(rc, o + j * 1024 + lane * 16, 0, LAUX);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        sum = dot2(v[j].x, 0x10001u, sum);
-        sum = dot2(v[j].y, 0x10001u, sum);
-        sum = dot2(v[j].z, 0x10001u, sum);
-        sum = dot2(v[j].w, 0x10001u, sum);
-      }
-    }
-    st.t_all += sum;
-  } else if constexpr ((ABL & kHeaderOnly) != 0) {
+  if constexpr ((ABL & kHeaderOnly) != 0) {
     // no segment stream: the record needs only the header lines
   } else {
-    if constexpr ((ABL & kSkipWaveGate) && (ABL & kSkipEmptyLoads)) {
-      // a frame whose extent ends before its second stream KiB: take the skipping form
-      const uint32_t e16 = (uint32_t)((st.end_rel & ~1) + 3) & ~3u;
-      const bool short_frame = live && e16 <= stream_start((uint64_t)win) + 1024;
-      constexpr int kFull = ABL & ~(kSkipEmptyLoads | kSkipWaveGate);
-      if (__ballot(short_frame) == 0) {
-        if constexpr ((ABL & kPipeStream) && !IDX) {
-          if (a.stride <= 2048) // no frame reaches past its two stream KiBs
-            stream_phase_pipelined<kFull, LAUX, IDX>(a.stride, wave_slot + a.ipa_off, (uint64_t)win, n_here, lane,
-                                                     st.end_rel, st.t_all, st.pad);
-          else
-            stream_phase<kFull, LAUX, IDX>(a.stride, wave_slot + a.ipa_off, (uint64_t)win, n_here, lane, st.end_rel,
-                                           st.t_all, st.pad);
-        } else {
+    // kSkipWaveGate: a wave with a frame whose extent ends before its second stream KiB takes the skipping
+    // form, a wave of full-size frames the form that issues every load
+    const uint32_t e16 = (uint32_t)((st.end_rel & ~1) + 3) & ~3u;
+    const bool short_frame = live && e16 <= stream_start((uint64_t)win) + 1024;
+    constexpr int kFull = ABL & ~(kSkipEmptyLoads | kSkipWaveGate);
+    if (__ballot(short_frame) == 0) {
+      if constexpr (!IDX) {
+        if (a.stride <= 2048) // no frame reaches past its two stream KiBs: kPipeStream
+          stream_phase_pipelined<kFull, LAUX, IDX>(a.stride, wave_slot + a.ipa_off, (uint64_t)win, n_here, lane,
+                                                   st.end_rel, st.t_all, st.pad);
+        else
           stream_phase<kFull, LAUX, IDX>(a.stride, wave_slot + a.ipa_off, (uint64_t)win, n_here, lane, st.end_rel,
                                          st.t_all, st.pad);
-        }
       } else {
-        stream_phase<ABL, LAUX, IDX>(a.stride, wave_slot + a.ipa_off, (uint64_t)win, n_here, lane, st.end_rel, st.t_all,
-                                     st.pad);
+        stream_phase<kFull, LAUX, IDX>(a.stride, wave_slot + a.ipa_off, (uint64_t)win, n_here, lane, st.end_rel,
+                                       st.t_all, st.pad);
       }
     } else {
       stream_phase<ABL, LAUX, IDX>(a.stride, wave_slot + a.ipa_off, (uint64_t)win, n_here, lane, st.end_rel, st.t_all,
                                    st.pad);
     }
   }
-  if constexpr (ABL & kLateProbe) probe_finish<ABL>(st.probe, live && !bad_off, a, st.conn_id, st.flags);
   if constexpr (ABL & kChainAux) { // the ack number and window << 16 | destination port, as stored
     if (live)
-      finish<MIS, ABL, SAUX>(a, st, f, win, bad_off, lds_recs ? lds_recs + lane : nullptr, h.template u32<MIS + 28>(),
+      finish<MIS, ABL, SAUX>(a, st, f, win, bad_off, nullptr, h.template u32<MIS + 28>(),
                              h.template u16<MIS + 22>() | (h.template u16<MIS + 34>() << 16));
   } else {
-    if (live) finish<MIS, ABL, SAUX>(a, st, f, win, bad_off, lds_recs ? lds_recs + lane : nullptr);
+    if (live) finish<MIS, ABL, SAUX>(a, st, f, win, bad_off, nullptr);
   }
 }
 
-// GRP = 1: one 64-frame group per workgroup, records stored as each group finishes.
-// GRP > 1 (tuning variants): GRP consecutive groups per workgroup, their records kept in
-// LDS and written in one GRP-KiB burst at the end (scripts/write_grouping.py probe).
-// GOPT (tuning): bit 0 = GRP groups per workgroup but records stored per group (no LDS);
-// bit 1 / bit 2 = register budget for 3 / 2 waves per SIMD instead of 4 (a budget for 5 spills and costs 8.6 %
-// on the round-3 final tree, profiles/r03/window/five_waves_c*.json);
-// GOPT >> 4 = KiB of LDS padding, which caps workgroups per CU.  Production pads 2 KiB:
-// with the 8-KiB window tile that is 10 KiB per workgroup, 16 per CU = 4 waves/SIMD where
-// registers allowed 5 before the grouped probe -- C2 -1.2 %, C3 -2.5 %, C5 -0.3 % (3 waves: C3 +9 %, C5 +13 %;
-// profiles/r01_experiments/occupancy_c{2,3,5}.json).
-// Bit 3: XCD-aware order.  Workgroup b is dispatched to XCD b % 8; mapping it to group
+// One 64-frame group per workgroup, its records stored as the group finishes.
+// GOPT bit 3: XCD-aware order.  Workgroup b is dispatched to XCD b % 8; mapping it to group
 // (b % 8) * ceil(G / 8) + b / 8 gives every XCD one contiguous eighth of the batch (its own
 // L2 and memory-side traffic stays in one region): C2 -1.2 %, C3 -4.2 %, C5 -3.4 %
 // (profiles/r01_experiments/xcd_order_c{2,3,5}.json; records identical).
+// GOPT >> 4 (bits 4-11) = KiB of LDS padding, which caps workgroups per CU.  Production pads 2 KiB:
+// with the 8-KiB window tile that is 10 KiB per workgroup, 16 per CU = 4 waves/SIMD where
+// registers allowed 5 before the grouped probe -- C2 -1.2 %, C3 -2.5 %, C5 -0.3 % (3 waves: C3 +9 %, C5 +13 %;
+// profiles/r01_experiments/occupancy_c{2,3,5}.json; a register budget for 5 spills and costs 8.6 %,
+// profiles/r03/window/five_waves_c*.json).
 constexpr int kXcdOrder = 8;
 constexpr int kProdGopt = (2 << 4) | kXcdOrder;
-// Bit 12: completion word (pn_classify_notify; signal_done in frame_pass.hpp).  Above the LDS-padding
-// field (bits 4-11).
+// Bit 12: completion word (pn_classify_notify; signal_done in frame_pass.hpp).
 constexpr int kSignalDone = 1 << 12;
-// Bit 13 (tuning): GRP consecutive groups per workgroup in XCD order, each group's records stored as it
-// finishes, so a group's store is in flight while the next group loads (only the last store is waited for at the
-// wave's end).  Bit 14: the lane index made opaque per group, so the compiler cannot hoist lane-derived values
-// out of the group loop (live across it they cost registers: 128-147 VGPRs in the GRP > 1 variants above).
-constexpr int kGroupLoopXcd = 1 << 13;
-constexpr int kOpaqueLane = 1 << 14;
+// The parameter list and the flags' values are frozen: the demangled kernel names are keys in
+// profiles/pmc_traffic.json.  GRP (groups per workgroup) and the other GOPT bits selected workgroup shapes
+// that were measured and retired ("Retired RX variants"), as were the ABL bits not named here.
+constexpr int kLiveAbl = kProdAbl | kAblNoProbe | kAblNoReduce | kHeaderOnly | kChainAux;
 template <int MIS, int COOP, int ABL = kProdAbl, int LAUX = kLoadAux, int SAUX = kStoreAux, int IDX = 0, int LWIN = LAUX,
           int GRP = 1, int GOPT = kProdGopt>
-__global__ __launch_bounds__(kWave, (GOPT & 4) ? 2 : (GOPT & 2) ? 3 : 4) void rx_classify_kernel(KArgs a) {
+__global__ __launch_bounds__(kWave, 4) void rx_classify_kernel(KArgs a) {
+  static_assert(GRP == 1 && (GOPT & kXcdOrder) && !(GOPT & ~(kXcdOrder | (0xff << 4) | kSignalDone)),
+                "one XCD-ordered group per workgroup: the other workgroup shapes are retired");
+  static_assert((ABL & kProdAbl) == kProdAbl && !(ABL & ~kLiveAbl), "a retired form of a phase");
   const int lane = threadIdx.x;
-  static_assert(!(GOPT & kSignalDone) || ((GOPT & 8) && GRP == 1), "the completion word is set on the XCD-ordered one-group path");
   if constexpr (((GOPT >> 4) & 0xff) > 0) {
     __shared__ uint32_t pad_lds[((GOPT >> 4) & 0xff) * 256];
     pad_lds[lane] = lane;
@@ -587,40 +500,12 @@ __global__ __launch_bounds__(kWave, (GOPT & 4) ? 2 : (GOPT & 2) ? 3 : 4) void rx
     // then wrapped each buffer load in a waterfall loop and serialized the window loads.
     if (__builtin_amdgcn_readfirstlane(pad_lds[(lane + 1) & 63]) == 0x7fffffffu) a.n = 0;
   }
-  if constexpr (GOPT & kGroupLoopXcd) {
-    const uint32_t g0 = xcd_group(blockIdx.x, gridDim.x) * GRP;
-#pragma nounroll
-    for (int g = 0; g < GRP; ++g) {
-      int l = lane;
-      if constexpr (GOPT & kOpaqueLane) asm volatile("" : "+v"(l));
-      classify_group<MIS, COOP, ABL, LAUX, SAUX, IDX, LWIN>(a, (g0 + g) * a.fpw, l, nullptr);
-    }
-  } else if constexpr (GOPT & 8) { // XCD-aware order (tuning): workgroup b runs on XCD b % 8; give each XCD a
-    // contiguous eighth of the batch instead of every eighth group
-    classify_group<MIS, COOP, ABL, LAUX, SAUX, IDX, LWIN>(a, xcd_group(blockIdx.x, gridDim.x) * a.fpw, lane, nullptr);
-    if constexpr (GOPT & kSignalDone) signal_done(a.sig_count, a.sig_flag, a.sig_token, lane);
-  } else if constexpr (GRP == 1 || (GOPT & 1)) {
-#pragma nounroll
-    for (int g = 0; g < GRP; ++g)
-      classify_group<MIS, COOP, ABL, LAUX, SAUX, IDX, LWIN>(a, (blockIdx.x * GRP + g) * a.fpw, lane, nullptr);
-  } else {
-    __shared__ u32x4 recs[GRP * kFramesPerWave];
-    const uint32_t first = blockIdx.x * GRP * kFramesPerWave;
-#pragma nounroll
-    for (int g = 0; g < GRP; ++g) // not unrolled: two groups' live ranges overlapping would halve occupancy
-      classify_group<MIS, COOP, ABL, LAUX, SAUX, IDX, LWIN>(a, first + g * kFramesPerWave, lane, recs + g * kFramesPerWave);
-    __syncthreads();
-    if (first >= a.n) return;
-    const uint32_t cnt = min((uint32_t)(GRP * kFramesPerWave), a.n - first);
-    const __amdgpu_buffer_rsrc_t ro = frame_rsrc((const uint8_t*)(a.out + first), cnt * 16); // stores past n dropped
-#pragma unroll
-    for (int g = 0; g < GRP; ++g)
-      __builtin_amdgcn_raw_buffer_store_b128(recs[g * kFramesPerWave + lane], ro, (g * kFramesPerWave + lane) * 16, 0, SAUX);
-  }
+  classify_group<MIS, COOP, ABL, LAUX, SAUX, IDX, LWIN>(a, xcd_group(blockIdx.x, gridDim.x) * a.fpw, lane);
+  if constexpr (GOPT & kSignalDone) signal_done(a.sig_count, a.sig_flag, a.sig_token, lane);
 }
-} // namespace
 
-namespace {
+// ---- host side: arguments and launches ----
+
 // Whether the cooperative header-window load applies: a 16-B chunk precedes the
 // window inside the slot (frame_off >= 2) and blocks are 16-B aligned.  One request
 // per block line: a single line for the default frame_off = 2 layout and ef_vi's
@@ -636,19 +521,52 @@ inline bool coop_layout(const KArgs& a) {
 // profiles/r01_experiments/indexed_window_policy_c{2,3,5}.json).
 constexpr int kIdxWin = 0;
 
-template <int MIS, int COOP, int ABL = kProdAbl, int LAUX = kLoadAux, int SAUX = kStoreAux, int IDX = 0, int LWIN = LAUX,
-          int GRP = 1, int GOPT = kProdGopt>
-void launch_one(const KArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((rx_classify_kernel<MIS, COOP, ABL, LAUX, SAUX, IDX, LWIN, GRP, GOPT>),
-                     dim3((a.n + GRP * a.fpw - 1) / (GRP * a.fpw)), dim3(kWave), 0, s, a);
+// The kernel arguments of a strided batch: n slots of `stride` bytes at `frames`, each frame's Ethernet header
+// frame_off into its slot, classified against the given conn-table snapshot.
+inline void strided_kargs(KArgs& a, const void* frames, void* out, const pn_conn_entry* tbl, uint64_t mask,
+                          uint32_t n_entries, uint32_t max_conn, uint32_t n, uint32_t stride, uint32_t frame_off) {
+  a.frames = (const uint8_t*)frames;
+  a.out = (pn_result*)out;
+  a.tbl = tbl;
+  a.mask = mask;
+  a.n_entries = n_entries;
+  a.max_conn = max_conn;
+  a.n = n;
+  a.stride = stride;
+  a.ipa_off = (frame_off + 14) & ~15u;
+  a.avail = stride - frame_off;
+  a.offs = nullptr;
+  a.fpw = frames_per_wave(n);
 }
 
+// f(std::integral_constant<int, MIS>{}) for the alignment class MIS = (off + 14) % 16 of an even Ethernet-header
+// offset: every launch of a kernel specialised on it goes through here.
+template <class F>
+void for_mis(uint32_t off, F&& f) {
+  switch ((off + 14) & 15) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    default: return f(std::integral_constant<int, 14>{});
+  }
+}
+
+template <int MIS, int COOP, int ABL = kProdAbl, int LAUX = kLoadAux, int SAUX = kStoreAux, int IDX = 0, int LWIN = LAUX,
+          int GOPT = kProdGopt>
+void launch_one(const KArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((rx_classify_kernel<MIS, COOP, ABL, LAUX, SAUX, IDX, LWIN, 1, GOPT>), dim3((a.n + a.fpw - 1) / a.fpw),
+                     dim3(kWave), 0, s, a);
+}
 
 template <int MIS, bool SIG = false, bool HO = false>
 void launch(const KArgs& a, hipStream_t s) {
   constexpr int G = SIG ? (kProdGopt | kSignalDone) : kProdGopt;
   constexpr int A = HO ? (kProdAbl | kHeaderOnly) : kProdAbl;
-  if (coop_layout(a)) return launch_one<MIS, 1, A, kLoadAux, kStoreAux, 0, kLoadAux, 1, G>(a, s);
-  launch_one<MIS, 0, A, kLoadAux, kStoreAux, 0, kLoadAux, 1, G>(a, s);
+  if (coop_layout(a)) return launch_one<MIS, 1, A, kLoadAux, kStoreAux, 0, kLoadAux, G>(a, s);
+  launch_one<MIS, 0, A, kLoadAux, kStoreAux, 0, kLoadAux, G>(a, s);
 }
 } // namespace

@@ -1,7 +1,7 @@
 // MI355X (gfx950) receive-path per-frame transform: the product C-ABI (pn_open /
 // pn_set_conn_table / pn_classify / pn_classify_indexed / pn_sync).  The kernel itself
-// and its execution model are in rx_classify.hpp; the tuning variants and bandwidth
-// ceilings live in the separate libpollnet_amd_tuning.so (rx_tuning.hip).
+// and its execution model are in rx_classify.hpp; the bandwidth ceilings live in the
+// separate libpollnet_amd_tuning.so (rx_tuning.hip).
 #include "rx_classify.hpp"
 
 namespace {
@@ -19,54 +19,22 @@ int strided_args(pn_ctx* ctx, const char* fn, const void* frames_dev, uint32_t s
     return set_err(ctx, PN_EINVAL, std::string(fn) + ": frames/results must be 16-byte aligned");
   if ((slot_stride & 15) || slot_stride > 65536 || (frame_off & 1) || slot_stride < frame_off + 96)
     return set_err(ctx, PN_EINVAL, std::string(fn) + ": slot_stride/frame_off violate the layout contract");
-  a.frames = (const uint8_t*)frames_dev;
-  a.out = (pn_result*)results_dev;
-  a.tbl = ctx->tbl_dev;
-  a.mask = ctx->mask;
-  a.n_entries = ctx->n_entries;
-  a.max_conn = ctx->max_conn;
-  a.n = n;
-  a.stride = slot_stride;
-  a.ipa_off = (frame_off + 14) & ~15u;
-  a.avail = slot_stride - frame_off;
-  a.offs = nullptr;
-  a.fpw = frames_per_wave(n);
+  strided_kargs(a, frames_dev, results_dev, ctx->tbl_dev, ctx->mask, ctx->n_entries, ctx->max_conn, n, slot_stride, frame_off);
   return PN_OK;
-}
-
-template <bool SIG, bool HO>
-void launch_strided_as(const KArgs& a, uint32_t frame_off, hipStream_t s) {
-  switch ((frame_off + 14) & 15) {
-    case 0: launch<0, SIG, HO>(a, s); break;
-    case 2: launch<2, SIG, HO>(a, s); break;
-    case 4: launch<4, SIG, HO>(a, s); break;
-    case 6: launch<6, SIG, HO>(a, s); break;
-    case 8: launch<8, SIG, HO>(a, s); break;
-    case 10: launch<10, SIG, HO>(a, s); break;
-    case 12: launch<12, SIG, HO>(a, s); break;
-    default: launch<14, SIG, HO>(a, s); break;
-  }
 }
 
 // the ctx's verify setting picks the full kernel or the header-only one (pn_set_verify)
 template <bool SIG>
 void launch_strided(const pn_ctx* ctx, const KArgs& a, uint32_t frame_off, hipStream_t s) {
-  if (ctx->verify_tcp) launch_strided_as<SIG, false>(a, frame_off, s);
-  else launch_strided_as<SIG, true>(a, frame_off, s);
+  for_mis(frame_off, [&](auto mis) {
+    if (ctx->verify_tcp) launch<mis(), SIG, false>(a, s);
+    else launch<mis(), SIG, true>(a, s);
+  });
 }
 
 template <int A>
 void launch_indexed(const KArgs& a, uint32_t eth_mod16, hipStream_t s) {
-  switch ((eth_mod16 + 14) & 15) {
-    case 0: launch_one<0, 1, A, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s); break;
-    case 2: launch_one<2, 1, A, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s); break;
-    case 4: launch_one<4, 1, A, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s); break;
-    case 6: launch_one<6, 1, A, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s); break;
-    case 8: launch_one<8, 1, A, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s); break;
-    case 10: launch_one<10, 1, A, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s); break;
-    case 12: launch_one<12, 1, A, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s); break;
-    default: launch_one<14, 1, A, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s); break;
-  }
+  for_mis(eth_mod16, [&](auto mis) { launch_one<mis(), 1, A, kLoadAux, kStoreAux, 1, kIdxWin, kXcdOrder>(a, s); });
 }
 
 } // namespace

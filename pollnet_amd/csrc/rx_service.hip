@@ -281,10 +281,9 @@ template <int MIS, int COOP, bool HELPER = false>
 __device__ __forceinline__ void svc_run(const KArgsAux& a, bool verify, bool linked, uint32_t w, uint32_t act, uint32_t k,
                                         uint32_t* done_word, int lane) {
   for (uint32_t g = w; g * a.fpw < a.n; g += act) {
-    if (verify) classify_group<MIS, COOP, kProdAbl | kChainAux, kLoadAux, kStoreAux, 0, kLoadAux>(a, g * a.fpw, lane, nullptr);
+    if (verify) classify_group<MIS, COOP, kProdAbl | kChainAux, kLoadAux, kStoreAux, 0, kLoadAux>(a, g * a.fpw, lane);
     else
-      classify_group<MIS, COOP, kProdAbl | kHeaderOnly | kChainAux, kLoadAux, kStoreAux, 0, kLoadAux>(a, g * a.fpw, lane,
-                                                                                                     nullptr);
+      classify_group<MIS, COOP, kProdAbl | kHeaderOnly | kChainAux, kLoadAux, kStoreAux, 0, kLoadAux>(a, g * a.fpw, lane);
   }
   if constexpr (HELPER) return;
   __threadfence_system();
@@ -499,33 +498,12 @@ void svc_publish(SvcPost* slot, const SvcPost& q, bool wc) {
 // the helper grid of large post k (its fields q), and the event its end completes: the post is done once both its
 // resident waves' done word and the grid's end are
 int svc_launch_helpers(pn_service* v, uint32_t k, uint32_t helpers, const SvcPost& q) {
-  const SvcPost* p = &q;
-  KArgsAux a;
-  a.n = p->n & kPostN;
-  a.fpw = p->fpw & 0xffu;
-  a.max_conn = p->max_conn;
-  a.frames = p->frames;
-  a.out = p->out;
-  a.tbl = p->tbl;
-  a.mask = p->mask;
-  a.n_entries = p->n_entries;
-  a.stride = v->stride;
-  a.ipa_off = (v->frame_off + 14) & ~15u;
-  a.avail = v->stride - v->frame_off;
-  a.offs = nullptr;
-  a.aux = nullptr;
-  const uint32_t verify = (p->n & kPostVerify) ? 1u : 0u, act = svc_active(a.n, a.fpw, kLatWaves + helpers);
+  KArgsAux a; // aux stays nullptr: a large post has no links
+  strided_kargs(a, q.frames, q.out, q.tbl, q.mask, q.n_entries, q.max_conn, q.n & kPostN, v->stride, v->frame_off);
+  a.fpw = q.fpw & 0xffu;
+  const uint32_t verify = (q.n & kPostVerify) ? 1u : 0u, act = svc_active(a.n, a.fpw, kLatWaves + helpers);
   hipStream_t s = v->helper_stream;
-  switch ((v->frame_off + 14) & 15) {
-    case 0: launch_helpers<0>(v->coop, helpers, a, verify, act, s); break;
-    case 2: launch_helpers<2>(v->coop, helpers, a, verify, act, s); break;
-    case 4: launch_helpers<4>(v->coop, helpers, a, verify, act, s); break;
-    case 6: launch_helpers<6>(v->coop, helpers, a, verify, act, s); break;
-    case 8: launch_helpers<8>(v->coop, helpers, a, verify, act, s); break;
-    case 10: launch_helpers<10>(v->coop, helpers, a, verify, act, s); break;
-    case 12: launch_helpers<12>(v->coop, helpers, a, verify, act, s); break;
-    default: launch_helpers<14>(v->coop, helpers, a, verify, act, s); break;
-  }
+  for_mis(v->frame_off, [&](auto mis) { launch_helpers<mis()>(v->coop, helpers, a, verify, act, s); });
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && !v->helper_ev[k & 1]) e = hipEventCreateWithFlags(&v->helper_ev[k & 1], hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventRecord(v->helper_ev[k & 1], s);
@@ -541,16 +519,7 @@ int svc_launch(pn_service* v, uint32_t base) {
   if (e != hipSuccess) return hip_err(ctx, e, "pn_service: device state");
   if (++v->epoch == 0) ++v->epoch;
   const SArgs a = svc_sargs(v, base);
-  switch ((v->frame_off + 14) & 15) {
-    case 0: launch_svc<0>(v->coop, kLatWaves, a, v->stream); break;
-    case 2: launch_svc<2>(v->coop, kLatWaves, a, v->stream); break;
-    case 4: launch_svc<4>(v->coop, kLatWaves, a, v->stream); break;
-    case 6: launch_svc<6>(v->coop, kLatWaves, a, v->stream); break;
-    case 8: launch_svc<8>(v->coop, kLatWaves, a, v->stream); break;
-    case 10: launch_svc<10>(v->coop, kLatWaves, a, v->stream); break;
-    case 12: launch_svc<12>(v->coop, kLatWaves, a, v->stream); break;
-    default: launch_svc<14>(v->coop, kLatWaves, a, v->stream); break;
-  }
+  for_mis(v->frame_off, [&](auto mis) { launch_svc<mis()>(v->coop, kLatWaves, a, v->stream); });
   e = hipGetLastError();
   if (e != hipSuccess) return hip_err(ctx, e, "pn_service: launch");
   v->running = true; // posts issued but not completed (still in their slots) run again on this launch (their helper

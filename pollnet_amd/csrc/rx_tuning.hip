@@ -1,8 +1,7 @@
-// Tuning library (libpollnet_amd_tuning.so, include/pollnet_amd_tuning.h): the RX kernel's
-// A/B variants (scripts/variants.py, history in profiles/r01_experiments) and the
-// same-run bandwidth ceilings bench.py reports beside the production kernel.  Never
-// linked into or loaded by the product path; the variants are compiled only with
-// `make` (TUNING=1 by default: -DPN_TUNING_VARIANTS; `make TUNING=0` leaves them out).
+// Tuning library (libpollnet_amd_tuning.so, include/pollnet_amd_tuning.h), RX side: the same-run
+// bandwidth ceilings bench.py reports beside the production kernel, the match-streams variants and
+// the spin / doorbell helpers.  Never linked into or loaded by the product path.  The classify
+// kernel's own A/B variants are retired ("Retired RX variants").
 #include "rx_classify.hpp"
 #include "stream_match.hpp"
 
@@ -185,73 +184,13 @@ __global__ __launch_bounds__(kWave) void calib_slot_read_var_kernel(const uint8_
   }
 }
 
-// Write-grouping probe: the slot-read ceiling with each 64-thread workgroup owning G
-// consecutive 64-slot groups and writing their G x 64 16-B records (G KiB, contiguous) in
-// one burst at the end instead of 1 KiB after each group.
-// EACH = true: the same G-group loop, records written after each group (separates the
-// effect of fewer, longer workgroups from that of the write bursts).
-template <int G, bool EACH = false>
-__global__ __launch_bounds__(kWave) void calib_slot_read_grouped_kernel(const uint8_t* base, uint32_t n, uint32_t stride,
-                                                                       uint32_t bytes, uint32_t* sink) {
-  __shared__ u32x4 recs[EACH ? 1 : G * kFramesPerWave];
-  const int lane = threadIdx.x;
-  for (int g = 0; g < G; ++g) {
-    const uint32_t wave_base = (blockIdx.x * G + g) * kFramesPerWave;
-    uint32_t acc = 0;
-    if (wave_base < n) {
-      const uint32_t n_here = min((uint32_t)kFramesPerWave, n - wave_base);
-      const uint8_t* wb = base + (uint64_t)wave_base * stride;
-      for (uint32_t b0 = 0; b0 < n_here; b0 += kBatch) {
-        u32x4 w0s[kBatch], w1s[kBatch];
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) {
-          const uint32_t nb = (b0 + j < n_here) ? bytes : 0u;
-          const __amdgpu_buffer_rsrc_t rs = frame_rsrc(wb + (uint64_t)(b0 + j) * stride, nb);
-          w0s[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, 0, kLoadAux);
-          w1s[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, 1024 + lane * 16, 0, kLoadAux);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) acc ^= w0s[j].x ^ w0s[j].y ^ w0s[j].z ^ w0s[j].w ^ w1s[j].x ^ w1s[j].y ^ w1s[j].z ^ w1s[j].w;
-      }
-    }
-    if constexpr (EACH) {
-      if (wave_base + lane < n) {
-        const __amdgpu_buffer_rsrc_t ro = frame_rsrc((const uint8_t*)(sink + 4 * (uint64_t)wave_base), 64 * 16);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{acc, acc ^ 1u, acc ^ 2u, acc ^ 3u}, ro, lane * 16, 0, kStoreAux);
-      }
-    } else {
-      recs[g * kFramesPerWave + lane] = u32x4{acc, acc ^ 1u, acc ^ 2u, acc ^ 3u};
-    }
-  }
-  if constexpr (EACH) return;
-  __syncthreads();
-  const uint32_t first = blockIdx.x * G * kFramesPerWave;
-  const __amdgpu_buffer_rsrc_t ro = frame_rsrc((const uint8_t*)(sink + 4 * (uint64_t)first),
-                                               16 * min((uint32_t)(G * kFramesPerWave), n - first));
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-    __builtin_amdgcn_raw_buffer_store_b128(recs[g * kFramesPerWave + lane], ro, (g * kFramesPerWave + lane) * 16, 0, kStoreAux);
-}
-
-// The production launch's arguments (rx_kernel.hip strided_args) for the ceilings below.
+// The production launch's arguments (strided_kargs) for the ceilings below.
 int strided_args_calib(pn_ctx* ctx, const void* frames_dev, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
                        void* results_dev, KArgs& a) {
   if (((uintptr_t)frames_dev & 15) || ((uintptr_t)results_dev & 15) || (slot_stride & 15) || slot_stride > 65536 ||
       slot_stride < frame_off + 96)
     return set_err(ctx, PN_EINVAL, "ceiling: layout contract");
-  a.frames = (const uint8_t*)frames_dev;
-  a.out = (pn_result*)results_dev;
-  a.tbl = ctx->tbl_dev;
-  a.mask = ctx->mask;
-  a.n_entries = ctx->n_entries;
-  a.max_conn = ctx->max_conn;
-  a.n = n;
-  a.stride = slot_stride;
-  a.ipa_off = (frame_off + 14) & ~15u;
-  a.avail = slot_stride - frame_off;
-  a.offs = nullptr;
-  a.fpw = frames_per_wave(n);
+  strided_kargs(a, frames_dev, results_dev, ctx->tbl_dev, ctx->mask, ctx->n_entries, ctx->max_conn, n, slot_stride, frame_off);
   if (!coop_layout(a)) return set_err(ctx, PN_EINVAL, "ceiling: needs the cooperative layout");
   return PN_OK;
 }
@@ -259,127 +198,6 @@ int strided_args_calib(pn_ctx* ctx, const void* frames_dev, uint32_t slot_stride
 } // namespace
 
 extern "C" {
-
-
-#ifdef PN_TUNING_VARIANTS
-// Tuning: the indexed kernel with the cooperative line window (variant 1) or without (0),
-// A/B-timed by scripts/bench_indexed.py; not part of the public header.
-int pn_classify_indexed_variant(pn_ctx* ctx, const void* base, const uint64_t* offsets, uint32_t eth_mod16, uint32_t n,
-                                uint32_t avail, void* results_dev, void* stream, int variant) {
-  if (!ctx || !ctx->tbl_dev || n == 0 || eth_mod16 != 2 || variant < 0 || variant > 5)
-    return set_err(ctx, PN_EINVAL, "indexed variant: bad args");
-  KArgs a;
-  a.frames = (const uint8_t*)base;
-  a.out = (pn_result*)results_dev;
-  a.tbl = ctx->tbl_dev;
-  a.mask = ctx->mask;
-  a.n_entries = ctx->n_entries;
-  a.max_conn = ctx->max_conn;
-  a.n = n;
-  a.stride = 0;
-  a.ipa_off = 0;
-  a.avail = avail;
-  a.offs = offsets;
-  a.fpw = frames_per_wave(n);
-  hipStream_t s = (hipStream_t)stream;
-  if (variant == 1) launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 1, kLoadAux, 1, kXcdOrder>(a, s); // window non-temporal
-  else if (variant == 2) launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 1, 0, 1, 0>(a, s);  // production window, blockIdx order
-  else if (variant == 3) launch_one<0, 1, kProdAbl, 0, kStoreAux, 1, 0, 1, 0>(a, s);         // + stream at default policy
-  else if (variant == 4) // timing only (packed captures): the wave's frames streamed as one contiguous range
-    launch_one<0, 1, kProdAbl | kAblContigStream, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s);
-  else if (variant == 5) // production without kSkipEmptyLoads (every stream load issued)
-    launch_one<0, 1, kProdAbl & ~kSkipEmptyLoads, kLoadAux, kStoreAux, 1, kIdxWin, 1, kXcdOrder>(a, s);
-  else launch_one<0, 0, kProdAbl, kLoadAux, kStoreAux, 1, kLoadAux, 1, 0>(a, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_err(ctx, e, "indexed variant launch");
-  pn_internal::note_stream(ctx, s);
-  return PN_OK;
-}
-
-
-int pn_classify_variant(pn_ctx* ctx, const void* frames_dev, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
-                        void* results_dev, void* stream, int variant) {
-  if (!ctx || !ctx->tbl_dev || (frame_off + 14) % 16 != 0 || n == 0) return set_err(ctx, PN_EINVAL, "variant: bad args");
-  KArgs a;
-  a.frames = (const uint8_t*)frames_dev;
-  a.out = (pn_result*)results_dev;
-  a.tbl = ctx->tbl_dev;
-  a.mask = ctx->mask;
-  a.n_entries = ctx->n_entries;
-  a.max_conn = ctx->max_conn;
-  a.offs = nullptr;
-  a.n = n;
-  a.stride = slot_stride;
-  a.ipa_off = (frame_off + 14) & ~15u;
-  a.avail = slot_stride - frame_off;
-  a.offs = nullptr;
-  a.fpw = frames_per_wave(n); // the product's launch shape
-  hipStream_t s = (hipStream_t)stream;
-  if ((variant & 1) && !coop_layout(a)) return set_err(ctx, PN_EINVAL, "variant: needs the cooperative layout");
-  // Tuning variants of the MIS = 0 (ip at slot+16) kernel, A/B-timed in one process by
-  // scripts/variants.py; not part of the public header.  History: profiles/r01_experiments.
-  switch (variant) {
-    case 0: launch_one<0, 0>(a, s); break;                         // per-lane window
-    case 1: launch_one<0, 1>(a, s); break;                         // cooperative window (production here)
-    case 2: launch_one<0, 0, kProdAbl, 0, 0>(a, s); break;                // per-lane, default cache policy
-    case 3: launch_one<0, 1, kProdAbl, 0, 0>(a, s); break;                // cooperative, default cache policy
-    case 4: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, 0>(a, s); break; // line-0 window default policy
-    case 5: launch_one<0, 1, kProdAbl, kLoadAux, 0>(a, s); break;         // default-policy record stores
-    case 6: launch_one<0, 1, kProdAbl, kLoadAux, 0, 0, 0>(a, s); break;   // both
-    case 7: launch_one<0, 1, kProdAbl, kLoadAux, 2>(a, s); break;         // nt record stores
-    case 8: launch_one<0, 1, kAblGlobalStore | kProdAbl>(a, s); break;        // plain global record store
-    case 9: launch_one<0, 1, 0>(a, s); break;                      // 16-B stream descriptors + per-dword tail masks
-    case 19: launch_one<0, 1, kAblStore8 | kProdAbl>(a, s); break;            // timing only: 8-B stores
-    case 22: launch_one<0, 1, kExactRange>(a, s); break;                         // scalar probe walk (before kCoopProbe)
-    case 23: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 2, 0>(a, s); break;  // 2 groups per WG, burst records
-    case 24: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 4, 0>(a, s); break;  // 4
-    case 25: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 8, 0>(a, s); break;  // 8
-    case 26: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 16, 0>(a, s); break; // 16
-    case 27: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 8, 1>(a, s); break;  // 8 groups, records per group
-    case 28: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 1, 2 << 4>(a, s); break;  // 1 group, +2 KiB LDS
-    case 29: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 1, 6 << 4>(a, s); break;  // 1 group, +6 KiB LDS
-    case 30: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 8, (2 << 4) | 1>(a, s); break;  // 27 + 2 KiB
-    case 31: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 1, 2>(a, s); break;  // 1 group, 3-wave budget
-    case 32: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 1, 4>(a, s); break;  // 1 group, 2-wave budget
-    case 33: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 2, 4>(a, s); break;  // 2 groups burst, 2-wave budget
-    case 34: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 1, 0>(a, s); break;  // no LDS pad: 5 waves/SIMD
-    case 35: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 1, kProdGopt | 8>(a, s); break;  // XCD-contiguous (production)
-    case 36: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 1, 2 << 4>(a, s); break;  // blockIdx order
-    case 37: launch_one<0, 1, kProdAbl & ~kSkipEmptyLoads>(a, s); break;  // every stream load issued (before kSkipEmptyLoads;
-    // the per-lane EXEC mask, per-batch gate and per-frame pair branch forms measured against it are
-    // in the history)
-    case 38: launch_one<0, 1, kProdAbl | kGroupProbe>(a, s); break;  // cluster lanes resolved per run position
-    case 39: launch_one<0, 1, kProdAbl & ~kGroupProbe>(a, s); break; // one lane per round trip past kAhead
-    case 42: launch_one<0, 1, kProdAbl | kLateProbe>(a, s); break;   // walk finished after phase 2
-    case 43: launch_one<0, 1, kProdAbl | kAblNoWalk>(a, s); break;   // timing only: home slot decides
-    case 45: launch_one<0, 1, kProdAbl | kAblNoWalk | kAblUniformProbe>(a, s); break; // timing only: one line per probe
-    case 47: launch_one<0, 1, kProdAbl | kSerialWindow>(a, s); break; // window loads one round trip each (before round 3)
-    case 48: launch_one<0, 1, kProdAbl & ~kPipeStream>(a, s); break;  // phase 2 not pipelined (before round 3)
-    case 11: launch_one<0, 1, kAblNoProbe | kProdAbl>(a, s); break;           // timing-only ablations from here
-    case 12: launch_one<0, 1, kAblNoReduce | kProdAbl>(a, s); break;
-    case 14: launch_one<0, 1, kAblNoMask>(a, s); break;
-    case 18: launch_one<0, 1, kAblNoStore | kProdAbl>(a, s); break;
-    case 49: launch_one<0, 1, kAblSmallStore | kProdAbl>(a, s); break;   // stores into 16 KiB
-    case 55: launch_one<0, 1, kAblEarlyStore | kProdAbl>(a, s); break;   // store issued first, none at the end
-    case 50: launch_one<0, 1, kProdAbl, kLoadAux, 1>(a, s); break;   // record stores sc0
-    case 51: launch_one<0, 1, kProdAbl, kLoadAux, 3>(a, s); break;   // sc0 nt
-    case 52: launch_one<0, 1, kProdAbl, kLoadAux, 17>(a, s); break;  // sc0 sc1
-    case 53: launch_one<0, 1, kProdAbl, kLoadAux, 18>(a, s); break;  // sc1 nt
-    case 54: launch_one<0, 1, kProdAbl, kLoadAux, 19>(a, s); break;  // sc0 sc1 nt
-    case 56: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 2, kProdGopt | kGroupLoopXcd | kOpaqueLane>(a, s); break;
-    case 57: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 4, kProdGopt | kGroupLoopXcd | kOpaqueLane>(a, s); break;
-    case 58: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 2, kProdGopt | kGroupLoopXcd>(a, s); break;
-    case 59: launch_one<0, 1, kProdAbl, kLoadAux, kStoreAux, 0, kLoadAux, 8, kProdGopt | kGroupLoopXcd | kOpaqueLane>(a, s); break;
-    default: return set_err(ctx, PN_EINVAL, "variant: unknown");
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_err(ctx, e, "variant launch");
-  pn_internal::note_stream(ctx, s);
-  return PN_OK;
-}
-
-
-#endif // PN_TUNING_VARIANTS
 
 // Same-run ceiling for pn_classify (bench.py): the production kernel -- its window loads, stream
 // loads, record stores, occupancy and workgroup order -- with the conn-table probe and the stream
@@ -409,12 +227,6 @@ int pn_calib_slot_read(pn_ctx* ctx, const void* src_dev, uint32_t n_slots, uint3
   const uint8_t* src = (const uint8_t*)src_dev;
   uint32_t* sink = (uint32_t*)sink_dev;
   switch (store_bytes) {
-    // 16 B records written per G groups (probe): store_bytes = 16 | G << 8
-    case 16 | (4 << 8): hipLaunchKernelGGL((calib_slot_read_grouped_kernel<4>), dim3((waves + 3) / 4), dim3(64), 0, s, src, n_slots, stride, bytes, sink); break;
-    case 16 | (16 << 8): hipLaunchKernelGGL((calib_slot_read_grouped_kernel<16>), dim3((waves + 15) / 16), dim3(64), 0, s, src, n_slots, stride, bytes, sink); break;
-    case 16 | (1 << 8): hipLaunchKernelGGL((calib_slot_read_grouped_kernel<1>), dim3(waves), dim3(64), 0, s, src, n_slots, stride, bytes, sink); break;
-    case 16 | (4 << 8) | (1 << 16): hipLaunchKernelGGL((calib_slot_read_grouped_kernel<4, true>), dim3((waves + 3) / 4), dim3(64), 0, s, src, n_slots, stride, bytes, sink); break;
-    case 16 | (16 << 8) | (1 << 16): hipLaunchKernelGGL((calib_slot_read_grouped_kernel<16, true>), dim3((waves + 15) / 16), dim3(64), 0, s, src, n_slots, stride, bytes, sink); break;
     case 16: hipLaunchKernelGGL((calib_slot_read_kernel<16>), dim3(waves), dim3(64), 0, s, src, n_slots, stride, bytes, sink); break;
     case 8: hipLaunchKernelGGL((calib_slot_read_kernel<8>), dim3(waves), dim3(64), 0, s, src, n_slots, stride, bytes, sink); break;
     default: hipLaunchKernelGGL((calib_slot_read_kernel<0>), dim3(waves), dim3(64), 0, s, src, n_slots, stride, bytes, sink);

@@ -36,8 +36,6 @@ _calib_rx_abl = _sig("pn_calib_classify_ablated", _i32, _vp, _vp, _u32, _u32, _u
 _calib_tx_abl = _sig("pn_calib_tx_ablated", _i32, _vp, _vp, _u32, _u32, _u32, _vp)
 _match_variant = _sig("pn_match_streams_variant", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _i32)
 _spin = _sig("pn_test_spin_wait", _i32, _vp, _vp, _u32, _vp)
-_variant = _sig("pn_classify_variant", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32)
-_idx_variant = _sig("pn_classify_indexed_variant", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32)
 _tx_variant = _sig("pn_tx_fill_variant", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _i32, _vp)
 
 
@@ -91,18 +89,6 @@ def spin_wait(go_host, done_host, max_ms: int, stream=None):
     done_host[0] = 1 (released) or 2 (timed out).  Uses no ctx."""
     rx._check(_spin(rx._ptr(go_host), rx._ptr(done_host), max_ms, rx._stream_handle(stream)), None,
               "pn_test_spin_wait")
-
-
-def classify_variant(ctx, frames_dev, slot_stride, frame_off, n, results_dev, stream, variant):
-    rx._check(_need(_variant, "pn_classify_variant")(ctx._h, rx._ptr(frames_dev), slot_stride, frame_off, n,
-                                                     rx._ptr(results_dev), rx._stream_handle(stream), variant),
-              ctx._h, "pn_classify_variant")
-
-
-def classify_indexed_variant(ctx, base, offsets, eth_mod16, n, avail, results, stream, variant):
-    rx._check(_need(_idx_variant, "pn_classify_indexed_variant")(ctx._h, rx._ptr(base), rx._ptr(offsets), eth_mod16, n,
-                                                                 avail, rx._ptr(results), rx._stream_handle(stream),
-                                                                 variant), ctx._h, "pn_classify_indexed_variant")
 
 
 def tx_fill_variant(ctx, frames_dev, slot_stride, frame_off, n, lens, variant, stream=None):

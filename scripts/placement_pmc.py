@@ -10,9 +10,9 @@ measurement, not part of any product path.
   placement_pmc.py run <out.json> [K]
   placement_pmc.py summarize <root_dir_with_pass_dirs_and_run_jsons> > summary.json
   placement_pmc.py orders <out.json> [K]   (no profiler) per buffer: the product kernel (XCD-contiguous
-      group order), the same kernel in blockIdx order (tuning variant 36) and a plain stream read of
-      the buffer, interleaved rounds -- is a slow placement slow for every access order, and for a
-      front-to-back read of all its bytes?"""
+      group order) and a plain stream read of the buffer, interleaved rounds -- is a slow placement
+      slow for a front-to-back read of all its bytes as well?  (The blockIdx-order and unpipelined
+      legs this had are retired with their kernels: DESIGN §4, "Retired RX variants".)"""
 import csv
 import ctypes as C
 import glob
@@ -175,8 +175,6 @@ def orders(out_path, k):
     sink = torch.zeros(4096, dtype=torch.int32, device="cuda")
     st = torch.cuda.current_stream()
     legs = {"product_xcd_order": lambda q: ctx.classify(q, stride, off, n, res, st),
-            "blockidx_order": lambda q: tn.classify_variant(ctx, q, stride, off, n, res, st, 36),
-            "no_pipe_stream": lambda q: tn.classify_variant(ctx, q, stride, off, n, res, st, 48),
             "stream_read": lambda q: tn.calib_stream_read(ctx, q, n * stride, sink, st)}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     times = [{name: [] for name in legs} for _ in ptrs]

@@ -19,7 +19,6 @@ def main():
     ap.add_argument("--config", type=int, default=2)
     ap.add_argument("--frames", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--variant", type=int, default=-1, help="tuning variant instead of the production kernel")
     a = ap.parse_args()
     import torch
 
@@ -37,10 +36,7 @@ def main():
     st = torch.cuda.current_stream()
     for _ in range(a.reps):
         tn.calib_stream_read(ctx, frames, frames.numel(), sink, st)
-        if a.variant < 0:
-            ctx.classify(frames, 2048, 2, a.frames, res, st)
-        else:
-            tn.classify_variant(ctx, frames, 2048, 2, a.frames, res, st, a.variant)
+        ctx.classify(frames, 2048, 2, a.frames, res, st)
     torch.cuda.synchronize()
     print(f"calib_bytes={frames.numel()} wire_bytes={pa.wire_bytes(s, 2048, 2, a.frames)} frames={a.frames}")
 
