@@ -13,13 +13,9 @@ GEN_LIB = pollnet_amd/libpollnet_amd_gen.so
 HDRS = include/pollnet_amd.h
 KHDRS = pollnet_amd/csrc/frame_pass.hpp pollnet_amd/csrc/device_common.hpp pollnet_amd/csrc/pn_internal.hpp \
   pollnet_amd/csrc/rx_classify.hpp pollnet_amd/csrc/tx_fill.hpp pollnet_amd/csrc/stream_match.hpp
-# measurement-only library (bench ceilings; A/B variants with TUNING=1): never loaded by the product
+# measurement-only library (bench ceilings, match-streams variants, test helpers): never loaded by the product
 TUNING_LIB = pollnet_amd/libpollnet_amd_tuning.so
 TUNING_SRCS = pollnet_amd/csrc/rx_tuning.hip pollnet_amd/csrc/tx_tuning.hip
-TUNING ?= 1
-ifeq ($(TUNING),1)
-TUNING_FLAGS = -DPN_TUNING_VARIANTS
-endif
 
 ORACLE = oracle/liboracle.so
 REFDIR ?= /root/reference
@@ -31,7 +27,6 @@ TCPRXBENCH = bench/bench_tcp_rx
 LATBENCH = bench/bench_latency
 SRVBENCH = bench/bench_tcp_server
 PINBENCH = bench/bench_pinned
-TXSMALLBENCH = bench/bench_tx_small
 # (defined before `all`: make expands a rule's prerequisites where the rule is read)
 SIGBENCH = bench/bench_signal
 STREAMBENCH = bench/bench_streams
@@ -144,10 +139,6 @@ $(SRVBENCH): bench/bench_tcp_server.cpp bench/sampler.hpp tests/cpp/segframes.hp
 	$(HOSTHIP) -O3 -g -std=c++17 -Wall -Wno-unused-result -o $@ $< -Lpollnet_amd -lpollnet_amd -Loracle -loracle \
 	  -Wl,-rpath,'$$ORIGIN/../pollnet_amd' -Wl,-rpath,'$$ORIGIN/../oracle'
 
-# TX fill at small batch sizes, one in-place launch vs two phases (variant 41: make TUNING=1; not in `all`)
-$(TXSMALLBENCH): bench/bench_tx_small.cpp $(HDRS) include/pollnet_amd_tuning.h $(LIB) $(TUNING_LIB) $(GEN_LIB)
-	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -lpollnet_amd_gen -lpollnet_amd_tuning -Wl,-rpath,'$$ORIGIN/../pollnet_amd'
-
 # completion by a polled word (pn_classify_notify) vs stream sync, small batches
 $(SIGBENCH): bench/bench_signal.cpp $(HDRS) $(LIB) $(GEN_LIB)
 	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -lpollnet_amd_gen -Wl,-rpath,'$$ORIGIN/../pollnet_amd'
@@ -194,7 +185,7 @@ $(GEN_LIB): pollnet_amd/csrc/framegen.cpp include/pollnet_amd_gen.h $(HDRS) $(LI
 	  -Wl,-rpath,'$$ORIGIN'
 
 $(TUNING_LIB): $(TUNING_SRCS) $(HDRS) include/pollnet_amd_tuning.h $(KHDRS)
-	$(HIPCC) $(HIPFLAGS) $(TUNING_FLAGS) -shared -o $@ $(TUNING_SRCS)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(TUNING_SRCS)
 
 $(ORACLE): oracle/pn_oracle.c oracle/pn_tx_oracle.c oracle/pn_oracle.h $(HDRS)
 	gcc $(CFLAGS_ORACLE) -shared -o $@ oracle/pn_oracle.c oracle/pn_tx_oracle.c -lpthread
@@ -203,7 +194,7 @@ ref:
 	@if [ -d $(REFDIR) ]; then $(MAKE) -C oracle -f ref.mk REFDIR=$(REFDIR); else echo "no $(REFDIR): using prebuilt oracle/_ref"; fi
 
 clean:
-	rm -f $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) oracle/_ref/*.so $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(TXSMALLBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(SERVERTEST) $(PEERTEST) $(CLISRVTEST) $(TXHOSTTEST) $(REFSERVERTEST) $(REFCONNTEST) $(REFCLIENTTEST)
+	rm -f $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) oracle/_ref/*.so $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(SERVERTEST) $(PEERTEST) $(CLISRVTEST) $(TXHOSTTEST) $(REFSERVERTEST) $(REFCONNTEST) $(REFCLIENTTEST)
 
 .PHONY: all ref clean svc_trace
 

@@ -2,9 +2,9 @@
  * pollnet_amd_tuning.h — measurement-only entry points (libpollnet_amd_tuning.so).
  *
  * NOT part of the product ABI (include/pollnet_amd.h) and never loaded by the product
- * path: same-run bandwidth ceilings that bench.py reports beside the production kernel,
- * and (unless built with `make TUNING=0`) the A/B variants of the TX fill that
- * scripts/tx_variants.py times.  Contexts come from pn_open().
+ * path: same-run bandwidth ceilings that bench.py reports beside the production kernels,
+ * the forms of pn_match_streams' kernel, and helpers for tests and latency probes.
+ * Contexts come from pn_open().
  */
 #ifndef POLLNET_AMD_TUNING_H
 #define POLLNET_AMD_TUNING_H
@@ -62,10 +62,6 @@ int pn_test_doorbell_echo(const uint32_t* bell_host, uint32_t* echo_host, uint32
  * of its arrival instead of up to a whole PCIe read round trip.  Values must increase (stale reads are ignored). */
 int pn_test_doorbell_echo_pipe(const uint32_t* bell_host, uint32_t* echo_host, uint32_t max_idle_ms, int depth,
                                uint32_t gap, void* stream);
-
-/* ---- A/B variants (built by default, TUNING=1; ids documented at their definitions) ---- */
-int pn_tx_fill_variant(pn_ctx* ctx, void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
-                       const uint16_t* lens, int variant, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@
 // transpose-reduced onto the frame's own lane.  Design and measurements: DESIGN.md §4.
 #pragma once
 
+#include <type_traits>
+
 #include "device_common.hpp"
 
 namespace pn_dev {
@@ -89,8 +91,7 @@ constexpr int kProdAbl = kExactRange | kCoopProbe | kGroupProbe | kSkipEmptyLoad
 // two lines, still 8 slots per instruction instead of one window per lane.
 // COOP = 0: each lane loads its own window (frame_off = 0, where no chunk precedes it).
 // The cooperative window's LDS tile: 64 slots x 128 B (8 KiB), chunk p of slot r at
-// r*8 + (p ^ (r&7)).  One static allocation per kernel; the TX fill writes patched
-// blocks back from it.
+// r*8 + (p ^ (r&7)).  One static allocation per kernel.
 __device__ __host__ __forceinline__ constexpr uint32_t coop_block(uint32_t ipa_off) { return ipa_off - 16; }
 __device__ __forceinline__ u32x4* coop_tile() {
   __shared__ u32x4 tile[kFramesPerWave * 8];
@@ -203,6 +204,22 @@ inline uint32_t frames_per_wave(uint32_t n) {
   uint32_t fpw = kFramesPerWave;
   while (fpw > 8 && (n + fpw - 1) / fpw < 1024) fpw >>= 1;
   return fpw;
+}
+
+// f(std::integral_constant<int, MIS>{}) for the alignment class MIS = (off + 14) % 16 of an even Ethernet-header
+// offset: every launch of a kernel specialised on it (RX classify, TX fill) goes through here.
+template <class F>
+void for_mis(uint32_t off, F&& f) {
+  switch ((off + 14) & 15) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    default: return f(std::integral_constant<int, 14>{});
+  }
 }
 
 // Completion word (pn_classify_notify / pn_tx_fill_notify): every workgroup makes its stores

@@ -539,22 +539,6 @@ inline void strided_kargs(KArgs& a, const void* frames, void* out, const pn_conn
   a.fpw = frames_per_wave(n);
 }
 
-// f(std::integral_constant<int, MIS>{}) for the alignment class MIS = (off + 14) % 16 of an even Ethernet-header
-// offset: every launch of a kernel specialised on it goes through here.
-template <class F>
-void for_mis(uint32_t off, F&& f) {
-  switch ((off + 14) & 15) {
-    case 0: return f(std::integral_constant<int, 0>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 6: return f(std::integral_constant<int, 6>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 10: return f(std::integral_constant<int, 10>{});
-    case 12: return f(std::integral_constant<int, 12>{});
-    default: return f(std::integral_constant<int, 14>{});
-  }
-}
-
 template <int MIS, int COOP, int ABL = kProdAbl, int LAUX = kLoadAux, int SAUX = kStoreAux, int IDX = 0, int LWIN = LAUX,
           int GOPT = kProdGopt>
 void launch_one(const KArgs& a, hipStream_t s) {

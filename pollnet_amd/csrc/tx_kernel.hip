@@ -1,23 +1,6 @@
 // TX checksum fill: the product entry points pn_tx_fill and
-// pn_tx_fill_notify.  Kernels and their design notes are in tx_fill.hpp; tuning variants in
-// tx_tuning.hip (tuning library).
+// pn_tx_fill_notify.  Kernels, launch helpers and their design notes are in tx_fill.hpp.
 #include "tx_fill.hpp"
-
-namespace {
-TArgs tx_args(pn_ctx* ctx, void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n, const uint16_t* lens) {
-  TArgs a;
-  a.frames = (uint8_t*)frames;
-  a.lens = lens;
-  a.n = n;
-  a.stride = slot_stride;
-  a.ipa_off = (frame_off + 14) & ~15u;
-  a.avail = slot_stride - frame_off;
-  a.frame_off = frame_off;
-  a.patch = (uint2*)ctx->tx_patch;
-  a.fpw = frames_per_wave(n);
-  return a;
-}
-} // namespace
 
 extern "C" int pn_tx_fill(pn_ctx* ctx, void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
                           const uint16_t* lens, uint32_t mode, void* stream) {
@@ -34,10 +17,7 @@ extern "C" int pn_tx_fill(pn_ctx* ctx, void* frames, uint32_t slot_stride, uint3
     if (rc) return rc;
   }
   const TArgs a = tx_args(ctx, frames, slot_stride, frame_off, n, lens);
-  const uint32_t mis = (frame_off + 14) & 15;
-  if (mode == PN_TX_TCP) launch_mode<PN_TX_TCP>(a, mis, s);
-  else if (mode == PN_TX_UDP_EFVI) launch_mode<PN_TX_UDP_EFVI>(a, mis, s);
-  else launch_mode<PN_TX_UDP>(a, mis, s);
+  for_tx_mode(mode, [&](auto m) { launch_mode<m()>(a, s); });
   e = hipGetLastError();
   if (e != hipSuccess) return hip_err(ctx, e, "tx_fill launch");
   pn_internal::note_stream(ctx, s);
@@ -62,11 +42,8 @@ extern "C" int pn_tx_fill_notify(pn_ctx* ctx, void* frames, uint32_t slot_stride
   if (rc) return rc;
   a.sig_flag = done_word;
   a.sig_token = token;
-  const uint32_t mis = (frame_off + 14) & 15;
   static_assert(PN_NOTIFY_MAX_FRAMES <= kTxInPlaceMaxFrames, "notify batches take the one-launch in-place form");
-  if (mode == PN_TX_TCP) launch_mis<PN_TX_TCP, 0, true>(a, mis, s);
-  else if (mode == PN_TX_UDP_EFVI) launch_mis<PN_TX_UDP_EFVI, 0, true>(a, mis, s);
-  else launch_mis<PN_TX_UDP, 0, true>(a, mis, s);
+  for_tx_mode(mode, [&](auto m) { launch<m(), 0, true>(a, s); });
   e = hipGetLastError();
   if (e != hipSuccess) return hip_err(ctx, e, "tx_fill (notify) launch");
   pn_internal::note_stream(ctx, s);

@@ -1,9 +1,8 @@
 """ctypes bindings for libpollnet_amd_tuning.so (include/pollnet_amd_tuning.h).
 
 Measurement only — never imported by the product path: the same-run bandwidth ceilings
-that bench.py reports beside the production kernel, and (library built with
-``make``, unless ``TUNING=0``) the A/B kernel variants the scripts under scripts/ time.  Every call
-takes an open ``RxContext`` (pn_open)."""
+that bench.py reports beside the production kernel, the forms of pn_match_streams' kernel and
+a test helper.  Every call but ``spin_wait`` takes an open ``RxContext`` (pn_open)."""
 from __future__ import annotations
 
 import ctypes
@@ -21,9 +20,7 @@ _lib = ctypes.CDLL(LIB_PATH)
 
 
 def _sig(name, res, *args):
-    fn = getattr(_lib, name, None)
-    if fn is None:  # the A/B variants exist only in a TUNING=1 build
-        return None
+    fn = getattr(_lib, name)  # every declared symbol is always built: a missing one fails the import
     fn.restype = res
     fn.argtypes = list(args)
     return fn
@@ -36,13 +33,6 @@ _calib_rx_abl = _sig("pn_calib_classify_ablated", _i32, _vp, _vp, _u32, _u32, _u
 _calib_tx_abl = _sig("pn_calib_tx_ablated", _i32, _vp, _vp, _u32, _u32, _u32, _vp)
 _match_variant = _sig("pn_match_streams_variant", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _i32)
 _spin = _sig("pn_test_spin_wait", _i32, _vp, _vp, _u32, _vp)
-_tx_variant = _sig("pn_tx_fill_variant", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _i32, _vp)
-
-
-def _need(fn, name):
-    if fn is None:
-        raise rx.PollnetError(f"{name} needs the tuning library built with its variants (`make`, not `make TUNING=0`)")
-    return fn
 
 
 def calib_stream_read(ctx, src_dev, nbytes: int, sink_dev, stream=None):
@@ -89,9 +79,3 @@ def spin_wait(go_host, done_host, max_ms: int, stream=None):
     done_host[0] = 1 (released) or 2 (timed out).  Uses no ctx."""
     rx._check(_spin(rx._ptr(go_host), rx._ptr(done_host), max_ms, rx._stream_handle(stream)), None,
               "pn_test_spin_wait")
-
-
-def tx_fill_variant(ctx, frames_dev, slot_stride, frame_off, n, lens, variant, stream=None):
-    rx._check(_need(_tx_variant, "pn_tx_fill_variant")(ctx._h, rx._ptr(frames_dev), slot_stride, frame_off, n,
-                                                       rx._ptr(lens), variant, rx._stream_handle(stream)),
-              ctx._h, "pn_tx_fill_variant")

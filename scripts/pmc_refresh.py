@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 TUNING = os.path.join(ROOT, "pollnet_amd", "libpollnet_amd_tuning.so")
 FAMILIES = ("rx_classify_kernel", "match_streams_mask_kernel", "tx_fill_kernel", "tx_patch_kernel",
-            "calib_stream_read_kernel", "tx_patch_wt_kernel", "tx_l2_release_kernel", "tx_patch_sector_kernel")
+            "calib_stream_read_kernel")
 
 
 def family(name):

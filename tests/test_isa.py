@@ -20,12 +20,10 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 @functools.lru_cache(maxsize=None)
 def _asm(src):
-    # the tuning library is built with its A/B variants (Makefile TUNING=1: -DPN_TUNING_VARIANTS)
-    extra = ["-DPN_TUNING_VARIANTS"] if "tuning" in src else []
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, os.path.basename(src) + ".s")
         subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S",
-                        *extra, os.path.join(ROOT, "pollnet_amd", "csrc", src), "-o", out], check=True,
+                        os.path.join(ROOT, "pollnet_amd", "csrc", src), "-o", out], check=True,
                        capture_output=True)
         with open(out) as f:
             return f.read()
