@@ -210,6 +210,69 @@ typedef struct pn_stream_filter { /* TcpStream::initFilter's four fields (TcpStr
 int pn_match_streams(pn_ctx* ctx, const void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
                      const pn_stream_filter* filters, uint32_t n_filters, uint32_t* stream_ids, void* stream);
 
+/* ---- UDP receive: subscription demux and checksum verdicts over a batch ----
+ * The receive side of pollnet's UDP surface (EfviUdpReceiver / SocketUdpReceiver, Efvi.h:132-273,
+ * Socket.h:394-493).  The reference installs one NIC filter per receiver object
+ * (ef_filter_spec_set_ip4_local(IPPROTO_UDP, ip, port), Efvi.h:143-156) and takes every field from fixed
+ * offsets of the frame the NIC hands it (Efvi.h:199, 252-253).  Here one launch does that filter for up to
+ * PN_UDP_MAX_SUBS (ip, port) pairs over a ring that carries everything on the wire, and gives the verdicts a
+ * NIC gives with EF_EVENT_TYPE_RX: the IPv4 header checksum and the RFC 768 UDP checksum.  The payload is read
+ * only of frames that matched a subscription, carry a checksum and are being verified: every other frame costs
+ * its header line.
+ *
+ * pn_udp_set_subs: a control-plane call.  subs is host memory; n_subs in [1, PN_UDP_MAX_SUBS]; a duplicate
+ *   (ip, port) pair or a non-zero _pad is PN_EINVAL.  No wildcards: dst_ip 0 matches only frames sent to
+ *   0.0.0.0.  It waits for every launch the ctx has issued (as pn_sync does), then replaces the device table,
+ *   and returns when the copy is done.  sub_id in the records of later launches indexes this array.
+ * pn_udp_classify: the layout contract of pn_classify (frames 16-byte aligned, slot_stride a multiple of 16 in
+ *   [frame_off + 96, 65536], frame_off even, avail = slot_stride - frame_off); frames and results in device
+ *   memory or pinned host memory; asynchronous on `stream`; n == 0 returns PN_OK.  Before pn_udp_set_subs:
+ *   PN_ENOTABLE.  pn_set_verify(ctx, 0) selects a header-only kernel (PN_UF_UDP_UNCHECKED).
+ * Every field of the record is computed from the fixed offsets for every frame, whatever the flags say. */
+#define PN_UDP_MAX_SUBS 4096u
+#define PN_UDP_NO_SUB 0xFFFFFFFFu
+typedef struct pn_udp_sub { /* ef_filter_spec_set_ip4_local(IPPROTO_UDP, ip, port), Efvi.h:143-156 */
+  uint32_t dst_ip;          /* network order, as stored in the frame */
+  uint16_t dst_port;        /* network order */
+  uint16_t _pad;            /* must be 0 */
+} pn_udp_sub;
+
+typedef struct pn_udp_result { /* 16 bytes, one per frame */
+  uint32_t sub_id;      /* index into the subs last set, PN_UDP_NO_SUB without PN_UF_MATCH */
+  uint32_t src_ip;      /* eth[26..30) as stored   (recvfrom's sin_addr.s_addr, Efvi.h:252) */
+  uint16_t src_port;    /* eth[34..36) as stored   (sin_port, Efvi.h:253) */
+  uint16_t payload_off; /* 42 = 14 + 20 + 8        (Efvi.h:140, :207) */
+  uint16_t payload_len; /* (uint16_t)(ntohs(udp->len) - 8)   (Efvi.h:199) */
+  uint16_t flags;       /* PN_UF_* below */
+} pn_udp_result;
+
+/* ulen = ntohs(udp->len) at eth[38..40), tot_len = ntohs(ip->tot_len).  "Checkable" = MATCH, not LEN_BAD, not
+ * TRUNC.  At most one of UDP_OK / NOCSUM / UDP_UNCHECKED is set. */
+#define PN_UF_IP_OK 0x0001u   /* the 20 bytes at ip fold to 0 (the same sum as PN_F_IP_OK) */
+#define PN_UF_UDP_OK 0x0002u  /* checkable, checksum field != 0, verifying on, and the RFC 768 sum folds to 0:
+                                 pseudo-header (src, dst, 17, ulen) + ulen bytes at ip + 20, an odd tail
+                                 zero-padded (the byte after the datagram has no influence); bytes between
+                                 ulen and tot_len - 20 are not summed; a transmitted 0xFFFF verifies like
+                                 any other value */
+#define PN_UF_MATCH 0x0004u   /* not NOT_UDP, IHL = 5, not FRAG, and (dst_ip, dst_port at eth[36..38)) is a
+                                 subscription */
+#define PN_UF_NOCSUM 0x0008u  /* checkable and the checksum field (eth[40..42)) is 0: RFC 768 "no checksum",
+                                 which Efvi's sender emits.  No payload byte is read. */
+#define PN_UF_FRAG 0x0010u    /* ntohs(frag_off) & 0x3FFF != 0 (MF set or a non-zero offset) */
+#define PN_UF_LEN_BAD 0x0020u /* ulen < 8, or tot_len < 28, or ulen > tot_len - 20 */
+#define PN_UF_IHL_NE_5 0x0200u   /* as PN_F_IHL_NE_5 */
+#define PN_UF_NOT_UDP 0x1000u    /* ether_type != 0x0800, or version != 4, or protocol != 17 */
+#define PN_UF_TRUNC 0x2000u      /* 34 + ((ulen + 1) & ~1) > avail (the rule of PN_F_TRUNC) */
+#define PN_UF_UDP_UNCHECKED 0x8000u /* checkable, checksum field != 0, and verifying off.  No payload byte
+                                       is read. */
+/* The frames a NIC would hand to EfviUdpReceiver::read as EF_EVENT_TYPE_RX. */
+#define PN_UDP_DELIVER(f) (((f) & PN_UF_MATCH) && ((f) & PN_UF_IP_OK) && \
+                           ((f) & (PN_UF_UDP_OK | PN_UF_NOCSUM | PN_UF_UDP_UNCHECKED)))
+
+int pn_udp_set_subs(pn_ctx* ctx, const pn_udp_sub* subs, uint32_t n_subs);
+int pn_udp_classify(pn_ctx* ctx, const void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
+                    void* results, void* stream);
+
 /* ---- TX checksum fill over a batch of outgoing frames ----
  * Replaces the reference's per-frame checksum finalisation on the send side:
  *   PN_TX_TCP      efvitcp: SendBuf::setOptDataLen (Core.h:157-163) at the end of

@@ -20,6 +20,11 @@ from .rx import (  # noqa: F401
     STREAM_FILTER_DTYPE,
     PN_NO_STREAM,
     PN_MAX_STREAM_FILTERS,
+    UDP_SUB_DTYPE,
+    UDP_RESULT_DTYPE,
+    PN_UDP_NO_SUB,
+    PN_UDP_MAX_SUBS,
+    UF,
     PN_SERVICE_WAVES,
     PN_SERVICE_WAVES_PER_CU,
     PN_SERVICE_MAX_WAVES,

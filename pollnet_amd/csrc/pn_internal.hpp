@@ -42,6 +42,11 @@ struct pn_ctx {
   void* sig_count = nullptr;         // pn_*_notify workgroup counters: [0] classify, [16] tx_fill (64-B apart)
   pn_fence sig[2];
   std::vector<pn_service*> services; // open resident services (pn_service_*): their posts capture table buffers
+  // UDP subscription table (pn_udp_set_subs): one device buffer of 8-B entries, replaced in place after a pn_sync
+  uint64_t* udp_tbl = nullptr;
+  uint32_t udp_cap = 0;  // entries allocated
+  uint32_t udp_mask = 0; // the current table's capacity - 1
+  uint32_t udp_n = 0;    // subscriptions in it (0: none set)
   std::string err;
 };
 

@@ -58,6 +58,35 @@ PN_NO_STREAM = 0xFFFFFFFF
 PN_MAX_STREAM_FILTERS = 64
 assert RESULT_DTYPE.itemsize == 16 and ENTRY_DTYPE.itemsize == 16 and STREAM_FILTER_DTYPE.itemsize == 16
 
+# pn_udp_sub / pn_udp_result: the UDP receive path (EfviUdpReceiver's filter and read / recvfrom fields, Efvi.h:143-268)
+UDP_SUB_DTYPE = np.dtype([("dst_ip", "<u4"), ("dst_port", "<u2"), ("_pad", "<u2")])
+UDP_RESULT_DTYPE = np.dtype([("sub_id", "<u4"), ("src_ip", "<u4"), ("src_port", "<u2"), ("payload_off", "<u2"),
+                             ("payload_len", "<u2"), ("flags", "<u2")])
+PN_UDP_NO_SUB = 0xFFFFFFFF
+PN_UDP_MAX_SUBS = 4096
+assert UDP_SUB_DTYPE.itemsize == 8 and UDP_RESULT_DTYPE.itemsize == 16
+
+
+class UF:
+    """pn_udp_result.flags bits (include/pollnet_amd.h)."""
+
+    IP_OK = 0x0001
+    UDP_OK = 0x0002
+    MATCH = 0x0004
+    NOCSUM = 0x0008
+    FRAG = 0x0010
+    LEN_BAD = 0x0020
+    IHL_NE_5 = 0x0200
+    NOT_UDP = 0x1000
+    TRUNC = 0x2000
+    UDP_UNCHECKED = 0x8000  # pn_set_verify(ctx, 0): a checksum was sent and not verified
+
+    @staticmethod
+    def deliver(flags):
+        """PN_UDP_DELIVER: the frames a NIC would hand to EfviUdpReceiver::read (scalar or numpy array)."""
+        f = np.asarray(flags)
+        return ((f & UF.MATCH) != 0) & ((f & UF.IP_OK) != 0) & ((f & (UF.UDP_OK | UF.NOCSUM | UF.UDP_UNCHECKED)) != 0)
+
 
 class PollnetError(RuntimeError):
     pass
@@ -121,6 +150,8 @@ _pn_tx_fill_notify = _sig("pn_tx_fill_notify", _i32, _vp, _vp, _u32, _u32, _u32,
 _pn_sync = _sig("pn_sync", _i32, _vp)
 _pn_set_verify = _sig("pn_set_verify", _i32, _vp, _i32)
 _pn_match_streams = _sig("pn_match_streams", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp)
+_pn_udp_set_subs = _sig("pn_udp_set_subs", _i32, _vp, _vp, _u32)
+_pn_udp_classify = _sig("pn_udp_classify", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
 _pn_service_open = _sig("pn_service_open", _i32, _vp, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_open_ex = _sig("pn_service_open_ex", _i32, _vp, _u32, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_post = _sig("pn_service_post", _i32, _vp, _vp, _u32, _vp, _vp)
@@ -346,6 +377,19 @@ class RxContext:
         flt = np.ascontiguousarray(filters, dtype=STREAM_FILTER_DTYPE)
         _check(_pn_match_streams(self._h, _ptr(frames), slot_stride, frame_off, n, flt.ctypes.data, len(flt),
                                  _ptr(stream_ids), _hold(self, stream)), self._h, "pn_match_streams")
+
+    def udp_set_subs(self, subs: np.ndarray):
+        """pn_udp_set_subs: the (dst_ip, dst_port) subscriptions (UDP_SUB_DTYPE, host array, network order) the
+        records of later udp_classify launches index.  A control-plane call: waits for every launch of the ctx."""
+        s = np.ascontiguousarray(subs, dtype=UDP_SUB_DTYPE)
+        _check(_pn_udp_set_subs(self._h, s.ctypes.data, len(s)), self._h, "pn_udp_set_subs")
+        self._held.clear()
+
+    def udp_classify(self, frames, slot_stride: int, frame_off: int, n: int, results, stream=None):
+        """pn_udp_classify: one UDP_RESULT_DTYPE record per frame (device or pinned memory): the subscription the
+        frame is for and its IPv4 / UDP checksum verdicts (UF).  Asynchronous on `stream`."""
+        _check(_pn_udp_classify(self._h, _ptr(frames), slot_stride, frame_off, n, _ptr(results), _hold(self, stream)),
+               self._h, "pn_udp_classify")
 
     def sync(self):
         """pn_sync: every stream this ctx launched on has drained."""
