@@ -7,13 +7,13 @@ CFLAGS_ORACLE = -O3 -march=x86-64-v3 -fPIC -Wall -std=c11
 
 LIB = pollnet_amd/libpollnet_amd.so
 SRCS = pollnet_amd/csrc/rx_kernel.hip pollnet_amd/csrc/rx_service.hip pollnet_amd/csrc/stream_kernel.hip pollnet_amd/csrc/tx_kernel.hip \
-  pollnet_amd/csrc/udp_kernel.hip pollnet_amd/csrc/conn_table.cpp
+  pollnet_amd/csrc/udp_kernel.hip pollnet_amd/csrc/udp_indexed_kernel.hip pollnet_amd/csrc/conn_table.cpp
 # the seeded workload generator (tests, bench): its own library, outside the product ABI
 GEN_LIB = pollnet_amd/libpollnet_amd_gen.so
 HDRS = include/pollnet_amd.h
 KHDRS = pollnet_amd/csrc/frame_pass.hpp pollnet_amd/csrc/device_common.hpp pollnet_amd/csrc/pn_internal.hpp \
   pollnet_amd/csrc/rx_classify.hpp pollnet_amd/csrc/tx_fill.hpp pollnet_amd/csrc/stream_match.hpp \
-  pollnet_amd/csrc/udp_classify.hpp
+  pollnet_amd/csrc/udp_classify.hpp pollnet_amd/csrc/udp_indexed.hpp
 # measurement-only library (bench ceilings, match-streams variants, test helpers): never loaded by the product
 TUNING_LIB = pollnet_amd/libpollnet_amd_tuning.so
 TUNING_SRCS = pollnet_amd/csrc/rx_tuning.hip pollnet_amd/csrc/tx_tuning.hip
@@ -44,6 +44,8 @@ REFCONNTEST = tests/cpp/test_ref_conn
 REFCLIENTTEST = tests/cpp/test_ref_client
 UDPRXTEST = tests/cpp/test_gpu_udp_rx
 UDPRXBENCH = bench/bench_udp_rx
+UDPRXIDXTEST = tests/cpp/test_gpu_udp_rx_indexed
+UDPLAYOUTTEST = tests/cpp/test_udp_ring_layout
 
 # Host programs that include HIP headers: compiled by hipcc with the device pass pinned to gfx950
 # (without --offload-arch hipcc would add a default-arch device pass for nothing)
@@ -61,13 +63,23 @@ CONN_INCS = $(addprefix oracle/_ref/,conn_tcpconn.inc conn_tcpserver.inc conn_ef
 HAVE_REF_TEXT = $(or $(wildcard $(REFDIR)/example/tcpserver.cc),$(and $(wildcard oracle/_ref/tcpserver_handler.inc),$(wildcard oracle/_ref/tcpclient_handler.inc)))
 REF_TESTS = $(if $(HAVE_REF_TEXT),$(SERVERTEST) $(CLISRVTEST) $(REFSERVERTEST) $(REFCONNTEST) $(REFCLIENTTEST))
 
-all: $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) ref $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(REF_TESTS) $(PEERTEST) $(TXHOSTTEST) $(UDPRXTEST) $(UDPRXBENCH)
+all: $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) ref $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(REF_TESTS) $(PEERTEST) $(TXHOSTTEST) $(UDPRXTEST) $(UDPRXBENCH) $(UDPRXIDXTEST) $(UDPLAYOUTTEST)
 
 # GpuUdpReceiver::poll / pollFrom vs a sequential host filter + the reference's read / recvfrom arithmetic (GPU)
 $(UDPRXTEST): tests/cpp/test_gpu_udp_rx.cpp include/pollnet_amd/udp_receiver.hpp include/pollnet_amd/gpu_rx.hpp $(HDRS) $(LIB)
 	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -Wl,-rpath,'$$ORIGIN/../../pollnet_amd'
 
-# pn_udp_classify on device-resident slots: verified, checksum-0 and 1-in-16-subscribed rings vs pn_classify, one run
+# GpuUdpReceiver::pollIndexed / pollFromIndexed over an EfviUdpRingLayout event run vs the sequential loop (GPU)
+$(UDPRXIDXTEST): tests/cpp/test_gpu_udp_rx_indexed.cpp include/pollnet_amd/udp_receiver.hpp include/pollnet_amd/rx_ring.hpp \
+  include/pollnet_amd/gpu_rx.hpp $(HDRS) $(LIB)
+	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -Wl,-rpath,'$$ORIGIN/../../pollnet_amd'
+
+# EfviUdpRingLayout's arithmetic vs the reference's, restated (host only)
+$(UDPLAYOUTTEST): tests/cpp/test_udp_ring_layout.cpp include/pollnet_amd/rx_ring.hpp
+	g++ -O2 -std=c++17 -Wall -o $@ $<
+
+# pn_udp_classify and pn_udp_classify_indexed on device-resident slots: verified, checksum-0 and 1-in-16-subscribed
+# rings, the verified and 1-in-16 rings again through the indexed entry point, vs pn_classify, one run
 $(UDPRXBENCH): bench/bench_udp_rx.cpp $(HDRS) $(LIB) $(GEN_LIB)
 	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -lpollnet_amd_gen -Wl,-rpath,'$$ORIGIN/../pollnet_amd'
 
@@ -205,7 +217,7 @@ ref:
 	@if [ -d $(REFDIR) ]; then $(MAKE) -C oracle -f ref.mk REFDIR=$(REFDIR); else echo "no $(REFDIR): using prebuilt oracle/_ref"; fi
 
 clean:
-	rm -f $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) oracle/_ref/*.so $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(SERVERTEST) $(PEERTEST) $(CLISRVTEST) $(TXHOSTTEST) $(REFSERVERTEST) $(REFCONNTEST) $(REFCLIENTTEST) $(UDPRXTEST) $(UDPRXBENCH)
+	rm -f $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) oracle/_ref/*.so $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(SERVERTEST) $(PEERTEST) $(CLISRVTEST) $(TXHOSTTEST) $(REFSERVERTEST) $(REFCONNTEST) $(REFCLIENTTEST) $(UDPRXTEST) $(UDPRXBENCH) $(UDPRXIDXTEST) $(UDPLAYOUTTEST)
 
 .PHONY: all ref clean svc_trace
 

@@ -1,10 +1,13 @@
-// pn_udp_classify on device-resident 2-KiB slots against pn_classify in the same run.
+// pn_udp_classify and pn_udp_classify_indexed on device-resident 2-KiB slots against pn_classify in the same run.
 //   a  every frame a 1514-B UDP datagram for one of 1024 subscriptions, valid non-zero checksum, verified
 //   b  the same frames sent with checksum 0 (Efvi's sender): one header line each
 //   c  one frame in 16 subscribed, the rest to other ports: only our own traffic is streamed
 //   d  pn_classify on C2 TCP frames of the same size (the generator's), the yardstick: (a) moves the same bytes
-// One process, the four legs interleaved step by step, HIP events around each launch, the median of `steps` after
-// warm-up; every leg's records are checked once.  One JSON line.
+//   e  (a)'s ring through pn_udp_classify_indexed with offsets[i] = i * stride + frame_off: what the indexed entry
+//      point costs over the strided one on the same bytes (e_over_a)
+//   f  (c)'s ring the same way (f_over_c)
+// One process, the six legs interleaved step by step, HIP events around each launch, the median of `steps` after
+// warm-up; every leg's records are checked once, (e) and (f) to be (a)'s and (c)'s byte for byte.  One JSON line.
 //   bench_udp_rx [steps = 30] [frames = 1048576]
 // (built by `make bench/bench_udp_rx`)
 #include <arpa/inet.h>
@@ -95,11 +98,17 @@ int main(int argc, char** argv) {
   if (pn_open(0, &ctx)) return std::fprintf(stderr, "%s\n", pn_last_error(nullptr)), 4;
   hipStream_t s;
   HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  constexpr int kLegs = 6;
   uint8_t* ring[4] = {};
-  void* rec[4] = {};
-  for (int l = 0; l < 4; l++) {
-    HIP(hipMalloc((void**)&ring[l], ring_bytes));
-    HIP(hipMalloc(&rec[l], (size_t)n * 16));
+  void* rec[kLegs] = {};
+  for (int l = 0; l < 4; l++) HIP(hipMalloc((void**)&ring[l], ring_bytes));
+  for (int l = 0; l < kLegs; l++) HIP(hipMalloc(&rec[l], (size_t)n * 16));
+  uint64_t* offs = nullptr; // legs e, f: every slot's Ethernet header, in slot order
+  HIP(hipMalloc((void**)&offs, (size_t)n * sizeof(uint64_t)));
+  {
+    std::vector<uint64_t> host(n);
+    for (uint32_t i = 0; i < n; i++) host[i] = (uint64_t)i * kStride + kOff;
+    HIP(hipMemcpy(offs, host.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
   }
 
   // legs a, b, c: host tiles of kTile distinct frames, repeated along the ring (every slot has its own address:
@@ -139,14 +148,16 @@ int main(int argc, char** argv) {
   }
 
   auto launch = [&](int l) {
-    return l < 3 ? pn_udp_classify(ctx, ring[l], kStride, kOff, n, rec[l], s) : pn_classify(ctx, ring[3], kStride, kOff, n, rec[3], s);
+    if (l < 3) return pn_udp_classify(ctx, ring[l], kStride, kOff, n, rec[l], s);
+    if (l == 3) return pn_classify(ctx, ring[3], kStride, kOff, n, rec[3], s);
+    return pn_udp_classify_indexed(ctx, ring[l == 4 ? 0 : 2], offs, kOff % 16, n, kStride - kOff, rec[l], s);
   };
   hipEvent_t ev0, ev1;
   HIP(hipEventCreate(&ev0));
   HIP(hipEventCreate(&ev1));
-  std::vector<float> ms[4];
+  std::vector<float> ms[kLegs];
   for (uint32_t step = 0; step < warmup + steps; step++) {
-    for (int l = 0; l < 4; l++) {
+    for (int l = 0; l < kLegs; l++) {
       HIP(hipEventRecord(ev0, s));
       if (launch(l)) return std::fprintf(stderr, "%s\n", pn_last_error(ctx)), 4;
       HIP(hipEventRecord(ev1, s));
@@ -171,6 +182,13 @@ int main(int argc, char** argv) {
         ok = ok && (r[i].flags & PN_UF_IP_OK) && r[i].payload_len == kPayload;
       }
     }
+    // the indexed legs wrote the strided legs' records
+    std::vector<pn_udp_result> r2(n);
+    for (int l = 4; l < kLegs; l++) {
+      HIP(hipMemcpy(r.data(), rec[l == 4 ? 0 : 2], (size_t)n * 16, hipMemcpyDeviceToHost));
+      HIP(hipMemcpy(r2.data(), rec[l], (size_t)n * 16, hipMemcpyDeviceToHost));
+      ok = ok && std::memcmp(r.data(), r2.data(), (size_t)n * 16) == 0;
+    }
     std::vector<pn_result> q(n);
     HIP(hipMemcpy(q.data(), rec[3], (size_t)n * 16, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; i++) tcp_ok += (q[i].flags & PN_F_TCP_OK) ? 1 : 0;
@@ -179,20 +197,22 @@ int main(int argc, char** argv) {
        udp_ok[2] == n / 16 && tcp_ok + (n + 1023) / 1024 >= n; // the generator damages one C2 frame in 1024
 
   const double a = median(ms[0]), b = median(ms[1]), c = median(ms[2]), d = median(ms[3]);
+  const double e_ms = median(ms[4]), f_ms = median(ms[5]);
   const double wire_bits = 8.0 * 1514 * n;
   std::printf(
       "{\"bench\": \"udp_rx\", \"frames\": %u, \"slot_stride\": %u, \"frame_bytes\": 1514, \"subscriptions\": %u, \"steps\": %u, "
       "\"warmup\": %u, \"a_verified_ms\": %.4f, \"b_checksum0_ms\": %.4f, \"c_one_in_16_ms\": %.4f, \"d_tcp_classify_ms\": %.4f, "
       "\"a_over_d\": %.4f, \"b_over_d\": %.4f, \"c_over_d\": %.4f, \"a_gbit_s\": %.1f, \"d_gbit_s\": %.1f, "
-      "\"a_min_ms\": %.4f, \"d_min_ms\": %.4f, \"ok\": %s}\n",
+      "\"a_min_ms\": %.4f, \"d_min_ms\": %.4f, \"e_indexed_verified_ms\": %.4f, \"f_indexed_one_in_16_ms\": %.4f, "
+      "\"e_over_a\": %.4f, \"f_over_c\": %.4f, \"e_min_ms\": %.4f, \"f_min_ms\": %.4f, \"ok\": %s}\n",
       n, kStride, kSubs, steps, warmup, a, b, c, d, a / d, b / d, c / d, wire_bits / (a * 1e6), wire_bits / (d * 1e6),
       (double)*std::min_element(ms[0].begin(), ms[0].end()), (double)*std::min_element(ms[3].begin(), ms[3].end()),
-      ok ? "true" : "false");
+      e_ms, f_ms, e_ms / a, f_ms / c, (double)*std::min_element(ms[4].begin(), ms[4].end()),
+      (double)*std::min_element(ms[5].begin(), ms[5].end()), ok ? "true" : "false");
   (void)hipStreamSynchronize(s);
-  for (int l = 0; l < 4; l++) {
-    (void)hipFree(ring[l]);
-    (void)hipFree(rec[l]);
-  }
+  for (int l = 0; l < 4; l++) (void)hipFree(ring[l]);
+  for (int l = 0; l < kLegs; l++) (void)hipFree(rec[l]);
+  (void)hipFree(offs);
   pn_close(ctx);
   return ok ? 0 : 1;
 }

@@ -228,6 +228,17 @@ int pn_match_streams(pn_ctx* ctx, const void* frames, uint32_t slot_stride, uint
  *   [frame_off + 96, 65536], frame_off even, avail = slot_stride - frame_off); frames and results in device
  *   memory or pinned host memory; asynchronous on `stream`; n == 0 returns PN_OK.  Before pn_udp_set_subs:
  *   PN_ENOTABLE.  pn_set_verify(ctx, 0) selects a header-only kernel (PN_UF_UDP_UNCHECKED).
+ * pn_udp_classify_indexed: the same record for frames that lie where RX events, a packet-mmap block or a packed
+ *   capture put them -- frame i's Ethernet header at base + offsets[i] -- under pn_classify_indexed's contract:
+ *   base 16-byte aligned, in device or pinned host memory; offsets n u64 values readable by the device;
+ *   eth_mod16 = offsets[i] % 16 for every i, even and below 16; avail in [96, 65536] bounds every read past the
+ *   Ethernet header (and takes the place of slot_stride - frame_off in PN_UF_TRUNC); a window that starts 16 B
+ *   into a 128-B line may also be read from that line's start, never below base.  Reads are dword-granular: the
+ *   aligned dword that holds byte avail - 1 may be read whole.  For the same frame bytes and the same avail the
+ *   record is pn_udp_classify's.  An offset outside the class gets {PN_UDP_NO_SUB, 0, 0, 0, 0, PN_UF_BADOFF} and
+ *   none of its bytes are read.  Records are written in offsets order.  For pollnet's ef_vi UDP ring
+ *   (EfviUdpReceiver, Efvi.h:140, 194-200) EfviUdpRingLayout (pollnet_amd/rx_ring.hpp) gives the arguments.
+ *   Asynchronous on `stream`; n == 0 returns PN_OK; before pn_udp_set_subs: PN_ENOTABLE; pn_set_verify as above.
  * Every field of the record is computed from the fixed offsets for every frame, whatever the flags say. */
 #define PN_UDP_MAX_SUBS 4096u
 #define PN_UDP_NO_SUB 0xFFFFFFFFu
@@ -263,6 +274,7 @@ typedef struct pn_udp_result { /* 16 bytes, one per frame */
 #define PN_UF_IHL_NE_5 0x0200u   /* as PN_F_IHL_NE_5 */
 #define PN_UF_NOT_UDP 0x1000u    /* ether_type != 0x0800, or version != 4, or protocol != 17 */
 #define PN_UF_TRUNC 0x2000u      /* 34 + ((ulen + 1) & ~1) > avail (the rule of PN_F_TRUNC) */
+#define PN_UF_BADOFF 0x4000u  /* pn_udp_classify_indexed: offset outside the call's eth_mod16 class; not parsed */
 #define PN_UF_UDP_UNCHECKED 0x8000u /* checkable, checksum field != 0, and verifying off.  No payload byte
                                        is read. */
 /* The frames a NIC would hand to EfviUdpReceiver::read as EF_EVENT_TYPE_RX. */
@@ -272,6 +284,8 @@ typedef struct pn_udp_result { /* 16 bytes, one per frame */
 int pn_udp_set_subs(pn_ctx* ctx, const pn_udp_sub* subs, uint32_t n_subs);
 int pn_udp_classify(pn_ctx* ctx, const void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
                     void* results, void* stream);
+int pn_udp_classify_indexed(pn_ctx* ctx, const void* base, const uint64_t* offsets, uint32_t eth_mod16,
+                            uint32_t n, uint32_t avail, void* results, void* stream);
 
 /* ---- TX checksum fill over a batch of outgoing frames ----
  * Replaces the reference's per-frame checksum finalisation on the send side:

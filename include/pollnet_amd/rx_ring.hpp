@@ -8,6 +8,9 @@
 //                   RX events name slots by id (Core.h:503-505).  The ring is
 //                   classified where the NIC wrote it: hipHostRegister it once, then
 //                   GpuRx/GpuTcpRx::pollIndexed(ring, offsets(ids), ...).
+//  EfviUdpRingLayout the same for pollnet's own UDP receiver (Efvi.h:66-92, 115-116, 140): 511 buffers
+//                   of 2048 B, the frame at 64 + prefix_len; for
+//                   GpuUdpReceiver::pollIndexed / pn_udp_classify_indexed.
 //  SocketEthBatcher pollnet's SocketEthReceiver (Socket.h:567-629): an AF_PACKET
 //                   SOCK_RAW ETH_P_ALL socket, non-blocking, bound to an interface,
 //                   optionally promiscuous; instead of one read() into one buffer per
@@ -45,6 +48,26 @@ struct EfviRingLayout {
   uint32_t avail() const { return kRecvBufSize - frame_off(); }
   uint64_t offset(uint32_t id) const { return (uint64_t)id * kRecvBufSize + frame_off(); }
   // offsets of a run of RX event ids (event order; wraps and gaps as the events have them)
+  void offsets(const uint32_t* ids, uint32_t n, uint64_t* out) const {
+    for (uint32_t i = 0; i < n; i++) out[i] = offset(ids[i]);
+  }
+};
+
+// pollnet's own ef_vi UDP ring (EfviReceiver / EfviUdpReceiver, Efvi.h:66-92, 115-116, 140, 194-200), as opposed to
+// efvitcp's above: N_BUF = 511 packet buffers of PKT_BUF_SIZE = 2048 B, the frame 64 B (the pkt_buf header's
+// cache line) + receive_prefix_len into its buffer; an RX event names its buffer by id.
+struct EfviUdpRingLayout {
+  static constexpr uint32_t kBufCnt = 511;      // N_BUF (Efvi.h:115)
+  static constexpr uint32_t kPktBufSize = 2048; // PKT_BUF_SIZE (Efvi.h:116)
+  static constexpr uint32_t kPktBufHdr = 64;    // the frame's place in a buffer before the prefix (Efvi.h:140)
+  uint32_t prefix_len = 0;                      // ef_vi_receive_prefix_len(&vi) (Efvi.h:140)
+
+  uint32_t frame_off() const { return kPktBufHdr + prefix_len; }
+  uint32_t eth_mod16() const { return frame_off() % 16; }
+  uint32_t avail() const { return kPktBufSize - frame_off(); }
+  size_t ring_bytes() const { return (size_t)kBufCnt * kPktBufSize; }
+  uint64_t offset(uint32_t id) const { return (uint64_t)id * kPktBufSize + frame_off(); }
+  // offsets of a run of RX event ids (event order; wraps, reposted ids and gaps as the events have them)
   void offsets(const uint32_t* ids, uint32_t n, uint64_t* out) const {
     for (uint32_t i = 0; i < n; i++) out[i] = offset(ids[i]);
   }

@@ -13,6 +13,9 @@
 // `data` points into the caller's ring (zero-copy, valid during the call).  Frames of no subscription are never
 // touched by the host.  Subscribed frames dropped for a bad IPv4 or UDP checksum are counted, as the
 // reference's applications count misses.
+// pollIndexed / pollFromIndexed take frames where RX events name them instead of a run of consecutive slots:
+// frame i's Ethernet header at ring + offsets[i] (pn_udp_classify_indexed) -- for pollnet's ef_vi ring,
+// EfviUdpRingLayout (rx_ring.hpp) turns a run of event ids into the offsets, eth_mod16 and avail.
 // Errors follow the reference: const char* (nullptr = ok).
 #pragma once
 
@@ -59,6 +62,9 @@ class GpuUdpReceiver {
       }
       if (hipHostMalloc((void**)&h_res_[b], sizeof(pn_udp_result) * (size_t)max_batch, hipHostMallocDefault) != hipSuccess)
         return "hipHostMalloc(results) failed";
+      if (mode == GpuRx::Mode::ZeroCopy &&
+          hipHostMalloc((void**)&h_offs_[b], sizeof(uint64_t) * (size_t)max_batch, hipHostMallocDefault) != hipSuccess)
+        return "hipHostMalloc(offsets) failed";
       if (hipEventCreateWithFlags(&done_[b], hipEventDisableTiming) != hipSuccess) return "hipEventCreate failed";
     }
     return nullptr;
@@ -87,7 +93,8 @@ class GpuUdpReceiver {
   // both counts under the IP one), since init.
   uint64_t droppedBadIpCsum() const { return drop_ip_; }
   uint64_t droppedBadUdpCsum() const { return drop_udp_; }
-  // ... and those with a good header checksum whose UDP length is impossible or runs past the slot
+  // ... and those with a good header checksum whose UDP length is impossible or runs past the slot (and, in an
+  // indexed poll, the frames whose offset is outside the call's alignment class: PN_UF_BADOFF)
   uint64_t droppedBadLength() const { return drop_len_; }
 
   template <class Handler>
@@ -98,52 +105,108 @@ class GpuUdpReceiver {
   // EfviUdpReceiver::recvfrom (Efvi.h:241-268): the source address from data - 16, the port from data - 8
   template <class Handler>
   const char* pollFrom(const uint8_t* slots, uint32_t n, Handler&& h) {
-    return run(slots, n, [&](uint32_t sub, const uint8_t* data, uint16_t len) {
-      struct sockaddr_in src_addr;
-      std::memset(&src_addr, 0, sizeof(src_addr));
-      src_addr.sin_family = AF_INET;
-      std::memcpy(&src_addr.sin_addr.s_addr, data - 16, 4);
-      std::memcpy(&src_addr.sin_port, data - 8, 2);
-      h((int)sub, data, len, (const struct sockaddr_in&)src_addr);
-    });
+    return run(slots, n, [&](uint32_t sub, const uint8_t* data, uint16_t len) { deliver_from(h, sub, data, len); });
+  }
+
+  // The frames where RX events put them (ZeroCopy only, as GpuRx::pollIndexed): frame i's Ethernet header at
+  // ring + offsets[i], every offsets[i] % 16 == eth_mod16 (even), avail = readable bytes from each Ethernet header
+  // (pn_udp_classify_indexed's contract; init's slot_stride / frame_off play no part).  `ring` is pinned host
+  // memory; `offsets` is any host memory, copied chunk by chunk into two pinned buffers of max_batch entries.
+  // Handler calls as poll's, in offsets order, data = ring + offsets[i] + 42.  An offset outside the class is not
+  // read and counts under droppedBadLength.
+  template <class Handler>
+  const char* pollIndexed(const uint8_t* ring, const uint64_t* offsets, uint32_t n, uint32_t eth_mod16, uint32_t avail,
+                          Handler&& h) {
+    return run_indexed(ring, offsets, n, eth_mod16, avail,
+                       [&](uint32_t sub, const uint8_t* data, uint16_t len) { h((int)sub, data, len); });
+  }
+  template <class Handler>
+  const char* pollFromIndexed(const uint8_t* ring, const uint64_t* offsets, uint32_t n, uint32_t eth_mod16,
+                              uint32_t avail, Handler&& h) {
+    return run_indexed(ring, offsets, n, eth_mod16, avail,
+                       [&](uint32_t sub, const uint8_t* data, uint16_t len) { deliver_from(h, sub, data, len); });
   }
 
   pn_ctx* ctx() { return ctx_; }
 
  private:
-  template <class Deliver>
-  const char* run(const uint8_t* slots, uint32_t n, Deliver&& deliver) {
-    if (n == 0 || subs_.empty()) return nullptr;
+  // EfviUdpReceiver::recvfrom (Efvi.h:251-255): the source address from data - 16, the port from data - 8
+  template <class Handler>
+  static void deliver_from(Handler& h, uint32_t sub, const uint8_t* data, uint16_t len) {
+    struct sockaddr_in src_addr;
+    std::memset(&src_addr, 0, sizeof(src_addr));
+    src_addr.sin_family = AF_INET;
+    std::memcpy(&src_addr.sin_addr.s_addr, data - 16, 4);
+    std::memcpy(&src_addr.sin_port, data - 8, 2);
+    h((int)sub, data, len, (const struct sockaddr_in&)src_addr);
+  }
+
+  // What every poll checks before its first launch.
+  const char* prepare(const uint8_t* ring) {
     if (mode_ == GpuRx::Mode::ZeroCopy) {
       hipPointerAttribute_t attr;
-      if (hipPointerGetAttributes(&attr, slots) != hipSuccess || attr.type != hipMemoryTypeHost)
+      if (hipPointerGetAttributes(&attr, ring) != hipSuccess || attr.type != hipMemoryTypeHost)
         return "zero-copy ring must be pinned host memory (hipHostMalloc / hipHostRegister)";
     }
     if (dirty_) { // nothing of this receiver is in flight between polls
       if (pn_udp_set_subs(ctx_, subs_.data(), (uint32_t)subs_.size())) return pn_last_error(ctx_);
       dirty_ = false;
     }
-    const char* e = run_chunks(slots, n, deliver);
+    return nullptr;
+  }
+
+  template <class Deliver>
+  const char* run(const uint8_t* slots, uint32_t n, Deliver&& deliver) {
+    if (n == 0 || subs_.empty()) return nullptr;
+    if (const char* e = prepare(slots)) return e;
+    const char* e = run_chunks(
+        n, [&](uint32_t k) { return launch(slots, n, k); },
+        [&](uint32_t i) { return slots + (size_t)i * stride_ + off_; }, deliver);
     if (e) (void)hipStreamSynchronize(stream_); // leave no chunk in flight
     return e;
   }
 
   template <class Deliver>
-  const char* run_chunks(const uint8_t* slots, uint32_t n, Deliver& deliver) {
+  const char* run_indexed(const uint8_t* ring, const uint64_t* offsets, uint32_t n, uint32_t eth_mod16, uint32_t avail,
+                          Deliver&& deliver) {
+    if (mode_ != GpuRx::Mode::ZeroCopy) return "pollIndexed needs Mode::ZeroCopy";
+    if (n == 0 || subs_.empty()) return nullptr;
+    if (!offsets) return "pollIndexed: offsets is NULL";
+    if (const char* e = prepare(ring)) return e;
+    auto launch_k = [&](uint32_t k) -> const char* {
+      const uint32_t base = k * cap_, m = std::min(cap_, n - base), b = k & 1;
+      std::memcpy(h_offs_[b], offsets + base, sizeof(uint64_t) * m); // buffer b is free: chunk k-2 was delivered
+      if (pn_udp_classify_indexed(ctx_, ring, h_offs_[b], eth_mod16, m, avail, h_res_[b], stream_))
+        return pn_last_error(ctx_);
+      if (hipEventRecord(done_[b], stream_) != hipSuccess) return "hipEventRecord failed";
+      return nullptr;
+    };
+    const char* e = run_chunks(n, launch_k, [&](uint32_t i) { return ring + offsets[i]; }, deliver);
+    if (e) (void)hipStreamSynchronize(stream_);
+    return e;
+  }
+
+  // The chunk pipeline of every poll: chunk k+1 is launched before chunk k is waited for and delivered.
+  // eth_of(i): frame i's Ethernet header.
+  template <class LaunchK, class EthOf, class Deliver>
+  const char* run_chunks(uint32_t n, LaunchK&& launch_k, EthOf&& eth_of, Deliver& deliver) {
     const uint32_t chunks = (n + cap_ - 1) / cap_;
-    if (const char* e = launch(slots, n, 0)) return e;
+    if (const char* e = launch_k(0)) return e;
     for (uint32_t k = 0; k < chunks; k++) {
       if (k + 1 < chunks)
-        if (const char* e = launch(slots, n, k + 1)) return e;
+        if (const char* e = launch_k(k + 1)) return e;
       if (hipEventSynchronize(done_[k & 1]) != hipSuccess) return "hipEventSynchronize failed";
       const uint32_t base = k * cap_, m = std::min(cap_, n - base);
       const pn_udp_result* res = h_res_[k & 1];
       for (uint32_t i = 0; i < m; i++) {
         const pn_udp_result& r = res[i];
+        if (r.flags & PN_UF_BADOFF) { // indexed polls only: an offset outside the class, nothing of it was read
+          drop_len_++;
+          continue;
+        }
         if (!(r.flags & PN_UF_MATCH)) continue;
         if (PN_UDP_DELIVER(r.flags)) {
-          const uint8_t* data = slots + (size_t)(base + i) * stride_ + off_ + r.payload_off;
-          deliver(r.sub_id, data, r.payload_len);
+          deliver(r.sub_id, eth_of(base + i) + r.payload_off, r.payload_len);
         } else if (!(r.flags & PN_UF_IP_OK)) {
           drop_ip_++;
         } else if (!(r.flags & (PN_UF_LEN_BAD | PN_UF_TRUNC))) {
@@ -177,6 +240,8 @@ class GpuUdpReceiver {
     for (int b = 0; b < 2; b++) {
       if (done_[b]) (void)hipEventDestroy(done_[b]);
       if (h_res_[b]) (void)hipHostFree(h_res_[b]);
+      if (h_offs_[b]) (void)hipHostFree(h_offs_[b]);
+      h_offs_[b] = nullptr;
       if (d_res_[b]) (void)hipFree(d_res_[b]);
       if (d_frames_[b]) (void)hipFree(d_frames_[b]);
       done_[b] = nullptr;
@@ -198,6 +263,7 @@ class GpuUdpReceiver {
   void* d_frames_[2] = {nullptr, nullptr};
   pn_udp_result* d_res_[2] = {nullptr, nullptr};
   pn_udp_result* h_res_[2] = {nullptr, nullptr};
+  uint64_t* h_offs_[2] = {nullptr, nullptr}; // ZeroCopy: pinned offsets the indexed kernel reads
   hipEvent_t done_[2] = {nullptr, nullptr};
   uint32_t stride_ = 0, off_ = 0, cap_ = 0;
   std::vector<pn_udp_sub> subs_;

@@ -2,7 +2,8 @@
 // the NIC filter of EfviUdpReceiver (ef_filter_spec_set_ip4_local(IPPROTO_UDP, ip, port), Efvi.h:143-156) for
 // thousands of subscriptions at once, the fields EfviUdpReceiver::read / recvfrom take from fixed offsets
 // (Efvi.h:199, 252-253), and the IPv4 / RFC 768 checksum verdicts a NIC gives with EF_EVENT_TYPE_RX.
-// Included by udp_kernel.hip only; everything is internal linkage.
+// Included by udp_kernel.hip and, for the subscription table and its probe, by udp_indexed.hpp (the indexed
+// kernel's own translation unit); everything is internal linkage.
 //
 // Same execution model as the RX classify kernel (rx_classify.hpp), built from the same frame pass
 // (frame_pass.hpp): one wave per 64 slots, one-wave workgroups in XCD order.

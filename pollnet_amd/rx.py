@@ -79,6 +79,7 @@ class UF:
     IHL_NE_5 = 0x0200
     NOT_UDP = 0x1000
     TRUNC = 0x2000
+    BADOFF = 0x4000  # udp_classify_indexed: an offset outside the call's eth_mod16 class, not parsed
     UDP_UNCHECKED = 0x8000  # pn_set_verify(ctx, 0): a checksum was sent and not verified
 
     @staticmethod
@@ -152,6 +153,7 @@ _pn_set_verify = _sig("pn_set_verify", _i32, _vp, _i32)
 _pn_match_streams = _sig("pn_match_streams", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp)
 _pn_udp_set_subs = _sig("pn_udp_set_subs", _i32, _vp, _vp, _u32)
 _pn_udp_classify = _sig("pn_udp_classify", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
+_pn_udp_classify_indexed = _sig("pn_udp_classify_indexed", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
 _pn_service_open = _sig("pn_service_open", _i32, _vp, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_open_ex = _sig("pn_service_open_ex", _i32, _vp, _u32, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_post = _sig("pn_service_post", _i32, _vp, _vp, _u32, _vp, _vp)
@@ -390,6 +392,17 @@ class RxContext:
         frame is for and its IPv4 / UDP checksum verdicts (UF).  Asynchronous on `stream`."""
         _check(_pn_udp_classify(self._h, _ptr(frames), slot_stride, frame_off, n, _ptr(results), _hold(self, stream)),
                self._h, "pn_udp_classify")
+
+    def udp_classify_indexed(self, base, offsets, eth_mod16: int, n: int, avail: int, results, stream=None):
+        """pn_udp_classify_indexed: udp_classify's record for frames at base + offsets[i] (u64; device or pinned
+        host memory), all with offsets[i] % 16 == eth_mod16; an offset outside that class gets the UF.BADOFF
+        record.  `avail` bounds every read past an Ethernet header.  Asynchronous on `stream`."""
+        _check(
+            _pn_udp_classify_indexed(self._h, _ptr(base), _ptr(offsets), eth_mod16, n, avail, _ptr(results),
+                                     _hold(self, stream)),
+            self._h,
+            "pn_udp_classify_indexed",
+        )
 
     def sync(self):
         """pn_sync: every stream this ctx launched on has drained."""
