@@ -287,6 +287,56 @@ int pn_udp_classify(pn_ctx* ctx, const void* frames, uint32_t slot_stride, uint3
 int pn_udp_classify_indexed(pn_ctx* ctx, const void* base, const uint64_t* offsets, uint32_t eth_mod16,
                             uint32_t n, uint32_t avail, void* results, void* stream);
 
+/* ---- UDP send: datagrams built in the slots of a TX ring from header templates ----
+ * The send side of pollnet's UDP surface (EfviUdpSender, Efvi.h:339-650).  The reference's write() is
+ * update_udp_pkt + memcpy into the next pkt_buf (Efvi.h:470-478, 611-621) for the one destination its object was
+ * initialised with.  Here one launch turns n messages in GPU-readable memory, each for one of up to
+ * PN_UDP_MAX_CHANNELS destinations, into n wire-ready frames in consecutive ring slots.
+ *
+ * pn_udp_set_channels: a control-plane call.  chans is host memory; n_chans in [1, PN_UDP_MAX_CHANNELS].  A
+ *   non-zero _pad, or a template that is not IPv4/UDP with IHL 5 (hdr[12..14) != 08 00, hdr[14] != 0x45,
+ *   hdr[23] != 17), refuses the whole set with PN_EINVAL before anything is waited for.  It then waits for every
+ *   launch the ctx has issued (as pn_sync does), replaces the one device table in place, and returns when the copy
+ *   is done.  The template's tot_len, IPv4 checksum, udp_len and UDP checksum fields are ignored: every build
+ *   writes them.  chan_ids of later builds index this array.
+ * pn_udp_build: asynchronous on `stream`.  Message i is the pay_lens[i] bytes at payloads + pay_offs[i], at any
+ *   byte alignment, for channel chan_ids[i] (chan_ids NULL: channel 0 for every message).  Its frame goes into slot
+ *   i, Ethernet header at frames + i*slot_stride + frame_off, under pn_classify's layout contract (frames 16-byte
+ *   aligned, slot_stride a multiple of 16 in [frame_off + 96, 65536], frame_off even).  Efvi's own pkt_buf ring is
+ *   frame_off = 8 (the ef_addr post_addr), slot_stride = 2048 (Efvi.h:588-594, 646-647).  payloads is 16-byte
+ *   aligned; payloads, frames, the index arrays and frame_lens are device or pinned host memory, each array
+ *   aligned to its element.
+ *   A built frame is the channel's 42 template bytes with tot_len = htons(28 + len), the IPv4 checksum per mode,
+ *   udp_len = htons(8 + len) and the UDP checksum per mode, then the len payload bytes at eth + 42;
+ *   frame_lens[i] = 42 + len (what the host hands to ef_vi_transmit*).  Nothing else is written and no ring byte
+ *   is read: every byte outside [eth, eth + 42 + len) keeps its value (the post_addr bytes, the slot's tail, the
+ *   neighbours), which the host or a NIC may own.
+ *   A message is refused when 42 + len > slot_stride - frame_off, or 42 + len > 65535 (frame_lens is 16 bits; so
+ *   28 + len always fits tot_len), or chan_ids[i] >= the channel count, or pay_offs[i] > payload_bytes, or
+ *   len > payload_bytes - pay_offs[i] (64-bit, no wrap).  A refused message gets frame_lens[i] = 0; no byte of its
+ *   slot is written and no byte of its payload is read.  No value in the index arrays makes the kernel touch memory
+ *   outside [payloads, payloads + round_up(payload_bytes, 16)), the n slots and the arrays; reads are
+ *   dword-granular: the aligned dword that holds a message's first or last byte may be read whole.  Payload ranges
+ *   may overlap or repeat (one message fanned out to many channels); frames must not overlap payloads.
+ *   n == 0 returns PN_OK; before pn_udp_set_channels: PN_ENOTABLE; an unknown mode, a NULL or misaligned pointer
+ *   or a broken layout contract: PN_EINVAL. */
+#define PN_UDP_MAX_CHANNELS 4096u
+typedef struct pn_udp_channel { /* 48 bytes */
+  uint8_t hdr[42];              /* EfviUdpSender::init_udp_pkt's result (Efvi.h:597-609): eth(14) ip(20) udp(8) */
+  uint8_t _pad[6];              /* must be 0 */
+} pn_udp_channel;
+
+#define PN_UB_EFVI 0u  /* ip checksum by Efvi's cached fold (Efvi.h:405-411, 615-617; the carry defect of
+                          DESIGN.md §12 included), udp checksum 0 -- byte for byte what write() leaves */
+#define PN_UB_PLAIN 1u /* ip checksum by CSum::fold (always verifies), udp checksum 0 */
+#define PN_UB_CSUM 2u  /* as PLAIN, plus the RFC 768 checksum over pseudo-header + udp header + payload, an odd
+                          tail zero-padded, a computed 0 sent as 0xFFFF */
+
+int pn_udp_set_channels(pn_ctx* ctx, const pn_udp_channel* chans, uint32_t n_chans);
+int pn_udp_build(pn_ctx* ctx, const void* payloads, uint64_t payload_bytes, const uint64_t* pay_offs,
+                 const uint16_t* pay_lens, const uint32_t* chan_ids, void* frames, uint32_t slot_stride,
+                 uint32_t frame_off, uint32_t n, uint32_t mode, uint16_t* frame_lens, void* stream);
+
 /* ---- TX checksum fill over a batch of outgoing frames ----
  * Replaces the reference's per-frame checksum finalisation on the send side:
  *   PN_TX_TCP      efvitcp: SendBuf::setOptDataLen (Core.h:157-163) at the end of

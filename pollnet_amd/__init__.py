@@ -24,6 +24,11 @@ from .rx import (  # noqa: F401
     UDP_RESULT_DTYPE,
     PN_UDP_NO_SUB,
     PN_UDP_MAX_SUBS,
+    UDP_CHANNEL_DTYPE,
+    PN_UDP_MAX_CHANNELS,
+    PN_UB_EFVI,
+    PN_UB_PLAIN,
+    PN_UB_CSUM,
     UF,
     PN_SERVICE_WAVES,
     PN_SERVICE_WAVES_PER_CU,

@@ -47,6 +47,10 @@ struct pn_ctx {
   uint32_t udp_cap = 0;  // entries allocated
   uint32_t udp_mask = 0; // the current table's capacity - 1
   uint32_t udp_n = 0;    // subscriptions in it (0: none set)
+  // UDP channel table (pn_udp_set_channels): one device buffer of 48-B entries, replaced in place after a pn_sync
+  uint32_t* ub_tbl = nullptr;
+  uint32_t ub_cap = 0; // channels allocated
+  uint32_t ub_n = 0;   // channels in it (0: none set)
   std::string err;
 };
 

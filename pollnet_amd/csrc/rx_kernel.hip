@@ -69,10 +69,12 @@ void pn_close(pn_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   // teardown: every launch that may still read ctx memory has finished.  A device-wide wait, so
   // that no stream handle is touched (the caller may have destroyed its streams already)
-  if (ctx->tbl_buf[0] || ctx->tbl_buf[1] || ctx->tx_patch || ctx->sig_count || ctx->udp_tbl) (void)hipDeviceSynchronize();
+  if (ctx->tbl_buf[0] || ctx->tbl_buf[1] || ctx->tx_patch || ctx->sig_count || ctx->udp_tbl || ctx->ub_tbl)
+    (void)hipDeviceSynchronize();
   for (pn_conn_entry* b : ctx->tbl_buf)
     if (b) (void)hipFree(b);
   if (ctx->udp_tbl) (void)hipFree(ctx->udp_tbl);
+  if (ctx->ub_tbl) (void)hipFree(ctx->ub_tbl);
   if (ctx->tx_patch) (void)hipFree(ctx->tx_patch);
   if (ctx->sig_count) (void)hipFree(ctx->sig_count);
   for (hipEvent_t ev : ctx->retired)

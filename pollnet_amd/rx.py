@@ -65,6 +65,13 @@ UDP_RESULT_DTYPE = np.dtype([("sub_id", "<u4"), ("src_ip", "<u4"), ("src_port", 
 PN_UDP_NO_SUB = 0xFFFFFFFF
 PN_UDP_MAX_SUBS = 4096
 assert UDP_SUB_DTYPE.itemsize == 8 and UDP_RESULT_DTYPE.itemsize == 16
+# pn_udp_channel: the UDP send path's per-destination header template (EfviUdpSender::init_udp_pkt, Efvi.h:597-609)
+UDP_CHANNEL_DTYPE = np.dtype([("hdr", "u1", (42,)), ("_pad", "u1", (6,))])
+PN_UDP_MAX_CHANNELS = 4096
+PN_UB_EFVI = 0   # ip checksum by Efvi's cached fold (carry defect included), udp checksum 0
+PN_UB_PLAIN = 1  # ip checksum by CSum::fold, udp checksum 0
+PN_UB_CSUM = 2   # as PLAIN plus the RFC 768 checksum (a computed 0 sent as 0xFFFF)
+assert UDP_CHANNEL_DTYPE.itemsize == 48
 
 
 class UF:
@@ -154,6 +161,8 @@ _pn_match_streams = _sig("pn_match_streams", _i32, _vp, _vp, _u32, _u32, _u32, _
 _pn_udp_set_subs = _sig("pn_udp_set_subs", _i32, _vp, _vp, _u32)
 _pn_udp_classify = _sig("pn_udp_classify", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
 _pn_udp_classify_indexed = _sig("pn_udp_classify_indexed", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
+_pn_udp_set_channels = _sig("pn_udp_set_channels", _i32, _vp, _vp, _u32)
+_pn_udp_build = _sig("pn_udp_build", _i32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp)
 _pn_service_open = _sig("pn_service_open", _i32, _vp, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_open_ex = _sig("pn_service_open_ex", _i32, _vp, _u32, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_post = _sig("pn_service_post", _i32, _vp, _vp, _u32, _vp, _vp)
@@ -402,6 +411,27 @@ class RxContext:
                                      _hold(self, stream)),
             self._h,
             "pn_udp_classify_indexed",
+        )
+
+    def udp_set_channels(self, chans: np.ndarray):
+        """pn_udp_set_channels: the 42-byte header templates (UDP_CHANNEL_DTYPE, host array) that chan_ids of later
+        udp_build launches index.  A control-plane call: waits for every launch of the ctx."""
+        c = np.ascontiguousarray(chans, dtype=UDP_CHANNEL_DTYPE)
+        _check(_pn_udp_set_channels(self._h, c.ctypes.data, len(c)), self._h, "pn_udp_set_channels")
+        self._held.clear()
+
+    def udp_build(self, payloads, payload_bytes: int, pay_offs, pay_lens, chan_ids, frames, slot_stride: int,
+                  frame_off: int, n: int, mode: int, frame_lens, stream=None):
+        """pn_udp_build: message i (pay_lens[i] bytes at payloads + pay_offs[i], any alignment) becomes a wire-ready
+        frame of channel chan_ids[i] (None: channel 0) in slot i of `frames`; frame_lens[i] = 42 + len, 0 for a
+        refused message.  Buffers in device or pinned memory; pay_offs u64, pay_lens / frame_lens u16, chan_ids
+        u32.  Asynchronous on `stream`."""
+        _check(
+            _pn_udp_build(self._h, _ptr(payloads), payload_bytes, _ptr(pay_offs), _ptr(pay_lens),
+                          None if chan_ids is None else _ptr(chan_ids), _ptr(frames), slot_stride, frame_off, n, mode,
+                          _ptr(frame_lens), _hold(self, stream)),
+            self._h,
+            "pn_udp_build",
         )
 
     def sync(self):
