@@ -1,8 +1,8 @@
-// The wave-per-64-slots frame pass shared by the RX classify kernel (rx_kernel.hip)
-// and the TX checksum fill (tx_kernel.hip): the 112-B header window of each slot
-// (cooperative line-0 LDS tile or per-lane loads) and the wave-wide stream of every
-// frame's summed extent past the window, with exact u16-word sums (v_dot2_u32_u16)
-// transpose-reduced onto the frame's own lane.  Design and measurements: DESIGN.md §4.
+// The wave-per-64-frames frame pass shared by the RX classify kernel (rx_classify.hpp), the UDP receive kernels
+// (udp_classify.hpp, udp_indexed.hpp) and the TX checksum fill (tx_fill.hpp): the 112-B header window of each
+// frame (cooperative LDS tile or per-lane loads; load_window_strided for slots, load_window_indexed for frames
+// named by offsets) and the wave-wide stream of every frame's summed extent past the window, with exact u16-word
+// sums (v_dot2_u32_u16) transpose-reduced onto the frame's own lane.  Design and measurements: DESIGN.md §4.
 #pragma once
 
 #include <type_traits>
@@ -167,6 +167,112 @@ __device__ __forceinline__ uint32_t load_window_strided(__amdgpu_buffer_rsrc_t r
     }
     if constexpr (MIS >= 2) ether_type = h.template u16<MIS - 2>();
     else ether_type = __builtin_amdgcn_raw_buffer_load_b32(rs, lo - 4, 0, LAUX) >> 16; // ipa_off >= 16 here
+  }
+  return ether_type;
+}
+
+// Indexed launches load the cooperative window blocks at the default cache policy (LWIN = 0): in a
+// packed capture a frame's last line is the next frame's window line, and a block loaded
+// with default policy is still in L2 when the previous frame's stream asks for it
+// (packed C2/C3/C5 -8..-10 %, permuted ef_vi event runs -2 %, in-order slot runs +1 %;
+// profiles/r01_experiments/indexed_window_policy_c{2,3,5}.json).
+constexpr int kIdxWin = 0;
+
+// Header window of this lane's frame for an indexed layout: the window (ip - MIS) at `win`, the frame's Ethernet
+// header `o` bytes past the base and `avail` bytes long at most.  Lanes without `use` (past n, or an offset outside
+// the launch's alignment class) read nothing and keep a zero window.  Returns the ether_type as stored.
+// Every lane of the workgroup must call it: with COOP it ballots and meets two barriers.
+// COOP = 1: when every used frame of the wave has its 128-B window block (the 16-B chunk before the window, and the
+// window) 16-B aligned inside [base, eth + avail), 8 lanes per frame load the block coalesced into the LDS tile, as
+// load_window_strided does (one request per line; the second line of a straddling block only when the header
+// fields reach it), at the default cache policy for LWIN = 0, else non-temporal.  Other waves, and COOP = 0, load
+// per lane: chunk c spans eth + (14 - MIS) + 16c .. +16 and is used only whole inside avail.
+// TAIL: the one chunk avail ends in is read as well, by the dwords that begin below avail (a datagram may end in it,
+// and an aligned dword lies in the page of its first byte).
+template <int MIS, int COOP, int LWIN, bool TAIL>
+__device__ __forceinline__ uint32_t load_window_indexed(const uint8_t* win, uint64_t o, bool use, uint32_t avail,
+                                                        int lane, Window& h) {
+  uint32_t ether_type = 0;
+#pragma unroll
+  for (int q = 0; q < 4 * kWinChunks; ++q) h.d[q] = 0;
+  bool coop = false; // wave-uniform
+  if constexpr (COOP) {
+    const bool elig = !use || ((((uintptr_t)win & 15u) == 0) && o + 14 >= (uint64_t)(MIS + 16) &&
+                               (uint32_t)(14 - MIS + kWinBytes) <= avail);
+    coop = __all(elig);
+  }
+  if (coop) {
+    __shared__ uint64_t line_addr[kFramesPerWave];
+    line_addr[lane] = use ? (uint64_t)(win - 16) : 0ull;
+    __syncthreads();
+    u32x4* tile = coop_tile();
+    // all 8 loads in flight before the first LDS write (as load_window_strided): a part that is not
+    // needed reads its block's first chunk instead -- a line the same instruction fetches anyway (or,
+    // for an unused row, the first used frame's block) -- and is zeroed, rather than a branch around it
+    const uint64_t used = __ballot(use);
+    const uint32_t l0 = used ? (uint32_t)__builtin_ctzll(used) : 0u;
+    const uint64_t wb = (uint64_t)(win - 16);
+    const uint64_t safe = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(wb >> 32), l0) << 32) |
+                          (uint32_t)__builtin_amdgcn_readlane((uint32_t)wb, l0);
+    u32x4 v[8];
+    bool need[8];
+    const u32x4* src[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint32_t r = 8 * i + (lane >> 3), part = lane & 7;
+      const uint64_t la = line_addr[r];
+      need[i] = la && block_part_needed<MIS>((uint32_t)la, part);
+      src[i] = need[i] ? reinterpret_cast<const u32x4*>(la) + part : reinterpret_cast<const u32x4*>(la ? la : safe);
+      v[i] = u32x4{0u, 0u, 0u, 0u};
+    }
+    if (used != 0) { // wave-uniform: a wave with no frame to classify loads nothing
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if constexpr (LWIN == 0) v[i] = *src[i];
+        else v[i] = __builtin_nontemporal_load(src[i]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint32_t r = 8 * i + (lane >> 3), part = lane & 7;
+      tile[r * 8 + (part ^ (r & 7))] = need[i] ? v[i] : u32x4{0u, 0u, 0u, 0u};
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < kWinChunks; ++c) {
+      const u32x4 v = tile[lane * 8 + ((1 + c) ^ (lane & 7))];
+      h.d[4 * c + 0] = v.x;
+      h.d[4 * c + 1] = v.y;
+      h.d[4 * c + 2] = v.z;
+      h.d[4 * c + 3] = v.w;
+    }
+    if constexpr (MIS >= 2) ether_type = h.template u16<MIS - 2>();
+    else ether_type = tile[lane * 8 + (0 ^ (lane & 7))].w >> 16;
+  } else if (use) {
+    // a chunk past avail re-reads chunk 0 (a line this lane fetches anyway) and is dropped, rather than a branch
+    // around its load, so the 7 loads are in flight together
+    u32x4 v[kWinChunks];
+#pragma unroll
+    for (int c = 0; c < kWinChunks; ++c) {
+      const bool in = (uint32_t)(14 - MIS + 16 * c + 16) <= avail;
+      v[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(win) + (in ? c : 0));
+    }
+#pragma unroll
+    for (int c = 0; c < kWinChunks; ++c) {
+      const uint32_t lo = (uint32_t)(14 - MIS + 16 * c); // the chunk's first byte, relative to eth
+      if (lo + 16 <= avail) {
+        h.d[4 * c + 0] = v[c].x;
+        h.d[4 * c + 1] = v[c].y;
+        h.d[4 * c + 2] = v[c].z;
+        h.d[4 * c + 3] = v[c].w;
+      } else if (TAIL && lo < avail) { // wave-uniform
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (lo + 4 * q < avail) h.d[4 * c + q] = reinterpret_cast<const uint32_t*>(win)[4 * c + q];
+      }
+    }
+    if constexpr (MIS >= 2) ether_type = h.template u16<MIS - 2>();
+    else ether_type = *reinterpret_cast<const uint32_t*>(win - 4) >> 16; // eth + 10 - MIS >= eth
   }
   return ether_type;
 }

@@ -313,14 +313,10 @@ __device__ __forceinline__ void finish(const KArgs& a, FrameState st, uint32_t f
 }
 
 // ---- the kernel: one 64-frame group per 64-thread workgroup ----
-// COOP = 1: 8 lanes per slot load its 128-B window block (the 16-B chunk before the
-// window + the window; the slot's first line in the default layout) into an
-// XOR-swizzled LDS tile that the header lanes read back (load_window_strided).
-// COOP = 0: each lane loads its own 112-B window (frame_off = 0).
+// COOP, LWIN: how the header windows are loaded (frame_pass.hpp: load_window_strided,
+// load_window_indexed); COOP = 0 is the strided frame_off = 0 layout.
 // IDX = 1: indexed layout (frame i at frames + offs[i], any place, same (offs+14)%16
-// class); per-frame stream descriptors; with COOP, waves whose frames all have their
-// block 16-B aligned inside the ring load blocks cooperatively, other waves per-lane
-// bounds-checked windows.
+// class; an offset outside the class is not parsed, PN_F_BADOFF); per-frame stream descriptors.
 // Register target: 4 waves/SIMD.  Until round 3 the MIS % 4 == 0 kernels fit 5 (<= 96 VGPRs) and the
 // LDS pad below held them at 4; the grouped probe takes them to 102 VGPRs (104 with the pipelined phase 2), so registers and pad agree.
 template <int MIS, int COOP, int ABL, int LAUX, int SAUX, int IDX, int LWIN>
@@ -338,96 +334,10 @@ __device__ __forceinline__ void classify_group(const KArgs& a, const uint32_t wa
   const uint8_t* win = nullptr; // this lane's window start (ip - MIS)
   bool bad_off = false;
   if constexpr (IDX) {
-    ether_type = 0;
-#pragma unroll
-    for (int q = 0; q < 4 * kWinChunks; ++q) h.d[q] = 0;
     const uint64_t o = live ? a.offs[f] : 0;
     bad_off = live && ((o + 14) & 15) != (uint64_t)MIS;
-    win = a.frames + o + 14 - MIS;
-    bool coop_done = false;
-    if constexpr (COOP) {
-      // Cooperative window: when every frame of the wave has its 128-B window block (the
-      // 16-B chunk before the window, and the window) 16-B aligned inside [base, eth + avail),
-      // 8 lanes per frame load the block coalesced into the LDS tile, as the strided kernel
-      // does (one request per line; the second line of a straddling block only when the
-      // header fields reach it); otherwise the wave falls back to per-lane windows.
-      const bool use = live && !bad_off;
-      const bool elig = !use || ((((uintptr_t)win & 15u) == 0) && o + 14 >= (uint64_t)(MIS + 16) &&
-                                 (uint32_t)(14 - MIS + kWinBytes) <= a.avail);
-      if (__all(elig)) {
-        __shared__ uint64_t line_addr[kFramesPerWave];
-        line_addr[lane] = use ? (uint64_t)(win - 16) : 0ull;
-        __syncthreads();
-        u32x4* tile = coop_tile();
-        // all 8 loads in flight before the first LDS write (as load_window_strided): a part that is not
-        // needed reads its block's first chunk instead -- a line the same instruction fetches anyway (or,
-        // for an unused row, the first used frame's block) -- and is zeroed, rather than a branch around it
-        const uint64_t used = __ballot(use);
-        const uint32_t l0 = used ? (uint32_t)__builtin_ctzll(used) : 0u;
-        const uint64_t wb = (uint64_t)(win - 16);
-        const uint64_t safe = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(wb >> 32), l0) << 32) |
-                              (uint32_t)__builtin_amdgcn_readlane((uint32_t)wb, l0);
-        u32x4 v[8];
-        bool need[8];
-        const u32x4* src[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const uint32_t r = 8 * i + (lane >> 3), part = lane & 7;
-          const uint64_t la = line_addr[r];
-          need[i] = la && block_part_needed<MIS>((uint32_t)la, part);
-          src[i] = need[i] ? reinterpret_cast<const u32x4*>(la) + part : reinterpret_cast<const u32x4*>(la ? la : safe);
-          v[i] = u32x4{0u, 0u, 0u, 0u};
-        }
-        if (used != 0) { // wave-uniform: a wave with no frame to classify loads nothing
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            if constexpr (LWIN == 0) v[i] = *src[i]; // default policy (tuning)
-            else v[i] = __builtin_nontemporal_load(src[i]);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const uint32_t r = 8 * i + (lane >> 3), part = lane & 7;
-          tile[r * 8 + (part ^ (r & 7))] = need[i] ? v[i] : u32x4{0u, 0u, 0u, 0u};
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < kWinChunks; ++c) {
-          const u32x4 v = tile[lane * 8 + ((1 + c) ^ (lane & 7))];
-          h.d[4 * c + 0] = v.x;
-          h.d[4 * c + 1] = v.y;
-          h.d[4 * c + 2] = v.z;
-          h.d[4 * c + 3] = v.w;
-        }
-        if constexpr (MIS >= 2) ether_type = h.template u16<MIS - 2>();
-        else ether_type = tile[lane * 8 + (0 ^ (lane & 7))].w >> 16;
-        coop_done = true;
-      }
-    }
-    if (live && !coop_done) {
-      if (!bad_off) {
-        // window chunk c spans eth + (14 - MIS) + 16c .. +16: used only inside avail.  A chunk past it
-        // re-reads chunk 0 (a line this lane fetches anyway) and is dropped, rather than a branch around
-        // its load, so the 7 loads are in flight together
-        u32x4 v[kWinChunks];
-#pragma unroll
-        for (int c = 0; c < kWinChunks; ++c) {
-          const bool in = (uint32_t)(14 - MIS + 16 * c + 16) <= a.avail;
-          v[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(win) + (in ? c : 0));
-        }
-#pragma unroll
-        for (int c = 0; c < kWinChunks; ++c) {
-          if ((uint32_t)(14 - MIS + 16 * c + 16) <= a.avail) {
-            h.d[4 * c + 0] = v[c].x;
-            h.d[4 * c + 1] = v[c].y;
-            h.d[4 * c + 2] = v[c].z;
-            h.d[4 * c + 3] = v[c].w;
-          }
-        }
-        if constexpr (MIS >= 2) ether_type = h.template u16<MIS - 2>();
-        else ether_type = *reinterpret_cast<const uint32_t*>(win - 4) >> 16; // eth + 10 - MIS >= eth
-      }
-    }
+    win = a.frames + o + 14 - MIS; // dereferenced by in-class live lanes only
+    ether_type = load_window_indexed<MIS, COOP, LWIN, false>(win, o, live && !bad_off, a.avail, lane, h);
   } else {
     ether_type = load_window_strided<MIS, COOP, LWIN>(rs, lane, a.stride, a.ipa_off, (uint32_t)(uintptr_t)wave_slot, h);
   }
@@ -513,13 +423,6 @@ __global__ __launch_bounds__(kWave, 4) void rx_classify_kernel(KArgs a) {
 inline bool coop_layout(const KArgs& a) {
   return (a.stride % 16) == 0 && a.ipa_off >= 16 && ((uintptr_t)a.frames % 16) == 0;
 }
-
-// Indexed launches load the cooperative window blocks at the default cache policy: in a
-// packed capture a frame's last line is the next frame's window line, and a block loaded
-// with default policy is still in L2 when the previous frame's stream asks for it
-// (packed C2/C3/C5 -8..-10 %, permuted ef_vi event runs -2 %, in-order slot runs +1 %;
-// profiles/r01_experiments/indexed_window_policy_c{2,3,5}.json).
-constexpr int kIdxWin = 0;
 
 // The kernel arguments of a strided batch: n slots of `stride` bytes at `frames`, each frame's Ethernet header
 // frame_off into its slot, classified against the given conn-table snapshot.

@@ -13,24 +13,18 @@ extern "C" {
 int pn_udp_classify_indexed(pn_ctx* ctx, const void* base, const uint64_t* offsets, uint32_t eth_mod16, uint32_t n,
                             uint32_t avail, void* results, void* stream) {
   if (!ctx) return set_err(nullptr, PN_EINVAL, "pn_udp_classify_indexed: ctx is NULL");
-  if (!ctx->udp_tbl || ctx->udp_n == 0)
-    return set_err(ctx, PN_ENOTABLE, "pn_udp_classify_indexed: no subscriptions (call pn_udp_set_subs)");
+  UdpIdxArgs a;
+  if (int rc = udp_common_args(ctx, "pn_udp_classify_indexed", results, n, a)) return rc;
   if (n == 0) return PN_OK;
   if (!base || !offsets || !results) return set_err(ctx, PN_EINVAL, "pn_udp_classify_indexed: NULL buffer");
   if (((uintptr_t)base & 15) || ((uintptr_t)results & 15) || ((uintptr_t)offsets & 7))
     return set_err(ctx, PN_EINVAL, "pn_udp_classify_indexed: base/results must be 16-byte, offsets 8-byte aligned");
   if (eth_mod16 > 15 || (eth_mod16 & 1) || avail < 96 || avail > 65536)
     return set_err(ctx, PN_EINVAL, "pn_udp_classify_indexed: eth_mod16 must be even < 16, avail in [96, 65536]");
-  UdpIdxArgs a;
   a.frames = (const uint8_t*)base;
-  a.out = (pn_udp_result*)results;
-  a.tbl = ctx->udp_tbl;
-  a.tbl_mask = ctx->udp_mask;
-  a.n = n;
   a.stride = 0;
   a.ipa_off = 0;
   a.avail = avail;
-  a.fpw = frames_per_wave(n);
   a.offs = offsets;
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipSetDevice(ctx->device);

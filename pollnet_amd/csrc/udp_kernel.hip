@@ -66,24 +66,18 @@ int pn_udp_set_subs(pn_ctx* ctx, const pn_udp_sub* subs, uint32_t n_subs) {
 int pn_udp_classify(pn_ctx* ctx, const void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n, void* results,
                     void* stream) {
   if (!ctx) return set_err(nullptr, PN_EINVAL, "pn_udp_classify: ctx is NULL");
-  if (!ctx->udp_tbl || ctx->udp_n == 0)
-    return set_err(ctx, PN_ENOTABLE, "pn_udp_classify: no subscriptions (call pn_udp_set_subs)");
+  UdpArgs a;
+  if (int rc = udp_common_args(ctx, "pn_udp_classify", results, n, a)) return rc;
   if (n == 0) return PN_OK;
   if (!frames || !results) return set_err(ctx, PN_EINVAL, "pn_udp_classify: NULL buffer");
   if (((uintptr_t)frames & 15) || ((uintptr_t)results & 15))
     return set_err(ctx, PN_EINVAL, "pn_udp_classify: frames/results must be 16-byte aligned");
   if ((slot_stride & 15) || slot_stride > 65536 || (frame_off & 1) || slot_stride < frame_off + 96)
     return set_err(ctx, PN_EINVAL, "pn_udp_classify: slot_stride/frame_off violate the layout contract");
-  UdpArgs a;
   a.frames = (const uint8_t*)frames;
-  a.out = (pn_udp_result*)results;
-  a.tbl = ctx->udp_tbl;
-  a.tbl_mask = ctx->udp_mask;
-  a.n = n;
   a.stride = slot_stride;
   a.ipa_off = (frame_off + 14) & ~15u;
   a.avail = slot_stride - frame_off;
-  a.fpw = frames_per_wave(n);
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
