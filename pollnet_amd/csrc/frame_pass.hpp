@@ -186,10 +186,11 @@ constexpr int kIdxWin = 0;
 // window) 16-B aligned inside [base, eth + avail), 8 lanes per frame load the block coalesced into the LDS tile, as
 // load_window_strided does (one request per line; the second line of a straddling block only when the header
 // fields reach it), at the default cache policy for LWIN = 0, else non-temporal.  Other waves, and COOP = 0, load
-// per lane: chunk c spans eth + (14 - MIS) + 16c .. +16 and is used only whole inside avail.
-// TAIL: the one chunk avail ends in is read as well, by the dwords that begin below avail (a datagram may end in it,
-// and an aligned dword lies in the page of its first byte).
-template <int MIS, int COOP, int LWIN, bool TAIL>
+// per lane: chunk c spans eth + (14 - MIS) + 16c .. +16 and is loaded whole when it lies inside avail; the one chunk
+// avail ends in is read by the dwords that begin below avail (a segment or datagram may end in it, and the header
+// lane sums the window below the stream start from these registers; an aligned dword lies in the page of its first
+// byte).
+template <int MIS, int COOP, int LWIN>
 __device__ __forceinline__ uint32_t load_window_indexed(const uint8_t* win, uint64_t o, bool use, uint32_t avail,
                                                         int lane, Window& h) {
   uint32_t ether_type = 0;
@@ -265,7 +266,7 @@ __device__ __forceinline__ uint32_t load_window_indexed(const uint8_t* win, uint
         h.d[4 * c + 1] = v[c].y;
         h.d[4 * c + 2] = v[c].z;
         h.d[4 * c + 3] = v[c].w;
-      } else if (TAIL && lo < avail) { // wave-uniform
+      } else if (lo < avail) { // wave-uniform
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           if (lo + 4 * q < avail) h.d[4 * c + q] = reinterpret_cast<const uint32_t*>(win)[4 * c + q];

@@ -337,7 +337,7 @@ __device__ __forceinline__ void classify_group(const KArgs& a, const uint32_t wa
     const uint64_t o = live ? a.offs[f] : 0;
     bad_off = live && ((o + 14) & 15) != (uint64_t)MIS;
     win = a.frames + o + 14 - MIS; // dereferenced by in-class live lanes only
-    ether_type = load_window_indexed<MIS, COOP, LWIN, false>(win, o, live && !bad_off, a.avail, lane, h);
+    ether_type = load_window_indexed<MIS, COOP, LWIN>(win, o, live && !bad_off, a.avail, lane, h);
   } else {
     ether_type = load_window_strided<MIS, COOP, LWIN>(rs, lane, a.stride, a.ipa_off, (uint32_t)(uintptr_t)wave_slot, h);
   }

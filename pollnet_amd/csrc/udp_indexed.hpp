@@ -34,7 +34,7 @@ __global__ __launch_bounds__(kWave, 4) void udp_indexed_kernel(UdpIdxArgs a) {
   const bool use = live && !bad_off;
   const uint8_t* win = a.frames + o + 14 - MIS; // ip - MIS; dereferenced by `use` lanes only
   Window h;
-  const uint32_t ether_type = load_window_indexed<MIS, 1, kIdxWin, true>(win, o, use, a.avail, lane, h);
+  const uint32_t ether_type = load_window_indexed<MIS, 1, kIdxWin>(win, o, use, a.avail, lane, h);
   const uint32_t s0 = stream_start((uint64_t)win);
   const UdpFrame fr = udp_header_phase<MIS, HO>(h, ether_type, use, a);
   uint32_t t_all = 0, pad = kPadUnknown;
