@@ -110,7 +110,9 @@ $(SERVERTEST): tests/cpp/test_tcp_server.cpp tests/cpp/segframes.hpp tests/cpp/s
 	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -Loracle -loracle \
 	  -Wl,-rpath,'$$ORIGIN/../../pollnet_amd' -Wl,-rpath,'$$ORIGIN/../../oracle'
 
-$(REF_INCS) $(CONN_INCS):
+# Behind `ref` (order-only), which extracts every one of them in one sub-make: a sub-make per file, run beside it
+# under -j, wrote each file a second time while a compile was reading it.  After `ref` the recipe finds its file up to date.
+$(REF_INCS) $(CONN_INCS): | ref
 	@if [ -d $(REFDIR) ]; then $(MAKE) -C oracle -f ref.mk REFDIR=$(REFDIR) $(@:oracle/%=%); \
 	else echo "$@: no $(REFDIR) to extract it from" >&2; exit 1; fi
 
