@@ -338,6 +338,52 @@ int pn_udp_build(pn_ctx* ctx, const void* payloads, uint64_t payload_bytes, cons
                  const uint16_t* pay_lens, const uint32_t* chan_ids, void* frames, uint32_t slot_stride,
                  uint32_t frame_off, uint32_t n, uint32_t mode, uint16_t* frame_lens, void* stream);
 
+/* ---- UDP gather: the delivered payloads of a classified ring packed in arrival order ----
+ * What EfviUdpReceiver::read hands its caller one datagram at a time (Efvi.h:194-207: a pointer to eth + 42 and
+ * a length), for a whole batch and for a consumer on the GPU: the payloads of the frames a pn_udp_classify call
+ * marked for delivery, copied out of their slots into one contiguous buffer, with the index arrays pn_udp_build
+ * takes as input (pay_offs, pay_lens, and sub_ids for chan_ids), so that a receive can feed a send without the host.
+ *
+ * pn_udp_gather: frames / slot_stride / frame_off under pn_udp_classify's layout contract, avail = slot_stride -
+ *   frame_off.  results: n pn_udp_result records, 16-byte aligned, normally the ones the classify call on the same
+ *   stream just wrote for these frames.
+ * pn_udp_gather_indexed: base / offsets / eth_mod16 / avail under pn_udp_classify_indexed's contract, the
+ *   dword-granular read rule included: the aligned dword that holds a payload's first or last byte may be read whole.
+ * Frame i is taken iff PN_UDP_DELIVER(results[i].flags), results[i].payload_off == 42 and 42 + results[i].payload_len
+ *   <= avail (and, indexed, offsets[i] % 16 == eth_mod16).  For a record the classify wrote for these frames the
+ *   last conditions always hold (DELIVER implies checkable, hence not TRUNC; an out-of-class offset is
+ *   PN_UF_BADOFF, never DELIVER): they are there so that no record value makes a kernel read outside
+ *   [eth, eth + avail) of its frame.  No byte of a frame that is not taken is read.
+ * The j-th taken frame in frame order is message j: pay_lens[j] = payload_len, sub_ids[j] = sub_id, src_index[j] = i
+ *   (src_index may be NULL), pay_offs[j] = the sum of round_up(len_k, PN_UDP_GATHER_ALIGN) over k < j; its len bytes
+ *   are copied from eth + 42 to payloads + pay_offs[j] and the bytes up to the next multiple of 16 are written as
+ *   zero, whatever follows the datagram in its slot.  total gets n_msgs, n_bytes = the sum over all messages (the
+ *   capacity needed) and n_fit.  A message with pay_offs[j] + round_up(len, 16) > payload_cap is not copied; its
+ *   index entries are still written.  Offsets ascend, so the copied messages are the first n_fit; n_fit == n_msgs
+ *   when n_bytes <= payload_cap.
+ * Nothing else is written: entries j >= n_msgs of the four arrays and the bytes of payloads past the last copied
+ *   message keep their value; no frame byte and no record is written.  No value in results or offsets makes a kernel
+ *   write outside [payloads, payloads + payload_cap), the first n entries of the arrays and total (j <= i always).
+ *   Records that change between the call's launches can garble the output, not escape it.
+ * payloads is 16-byte aligned and payload_cap a multiple of 16 (0 is allowed); each array is aligned to its element,
+ *   total to 8 bytes; every buffer is device or pinned host memory.  Asynchronous on `stream`: three launches, the
+ *   output deterministic.  Needs no subscription or channel table.  n == 0 returns PN_OK with total zeroed on the
+ *   stream and nothing else written.  A NULL pointer, a misaligned pointer or a broken layout contract: PN_EINVAL. */
+#define PN_UDP_GATHER_ALIGN 16u
+typedef struct pn_udp_gather_total { /* 16 bytes */
+  uint64_t n_bytes; /* bytes the taken messages need: the sum of round_up(len, 16) */
+  uint32_t n_msgs;  /* taken frames */
+  uint32_t n_fit;   /* leading messages whose bytes were copied (== n_msgs when n_bytes <= payload_cap) */
+} pn_udp_gather_total;
+
+int pn_udp_gather(pn_ctx* ctx, const void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
+                  const void* results, void* payloads, uint64_t payload_cap, uint64_t* pay_offs, uint16_t* pay_lens,
+                  uint32_t* sub_ids, uint32_t* src_index, pn_udp_gather_total* total, void* stream);
+int pn_udp_gather_indexed(pn_ctx* ctx, const void* base, const uint64_t* offsets, uint32_t eth_mod16, uint32_t n,
+                          uint32_t avail, const void* results, void* payloads, uint64_t payload_cap,
+                          uint64_t* pay_offs, uint16_t* pay_lens, uint32_t* sub_ids, uint32_t* src_index,
+                          pn_udp_gather_total* total, void* stream);
+
 /* ---- TX checksum fill over a batch of outgoing frames ----
  * Replaces the reference's per-frame checksum finalisation on the send side:
  *   PN_TX_TCP      efvitcp: SendBuf::setOptDataLen (Core.h:157-163) at the end of

@@ -16,6 +16,9 @@
 // pollIndexed / pollFromIndexed take frames where RX events name them instead of a run of consecutive slots:
 // frame i's Ethernet header at ring + offsets[i] (pn_udp_classify_indexed) -- for pollnet's ef_vi ring,
 // EfviUdpRingLayout (rx_ring.hpp) turns a run of event ids into the offsets, eth_mod16 and avail.
+// gather / gatherIndexed are poll / pollIndexed for a consumer on the GPU: instead of one handler call per datagram,
+// the delivered payloads of one batch packed in order into a device buffer, with the index arrays
+// GpuUdpSender::buildDevice (pn_udp_build) takes (pn_udp_gather).
 // Errors follow the reference: const char* (nullptr = ok).
 #pragma once
 
@@ -127,9 +130,132 @@ class GpuUdpReceiver {
                        [&](uint32_t sub, const uint8_t* data, uint16_t len) { deliver_from(h, sub, data, len); });
   }
 
+  // What a gather leaves on the device: message j (the j-th delivered frame of the batch, in ring / offsets order)
+  // is lens[j] bytes at payloads + offs[j], 16-byte aligned and zero-padded to a multiple of 16, for subscription
+  // subs[j], from frame src_index[j].  n_bytes is the room the n_msgs messages need; the first n_fit were copied
+  // (all of them: the receiver's buffer holds max_batch datagrams of the largest size the layout allows).  The
+  // pointers are device pointers into the receiver's own buffers, valid until its next gather or init.
+  struct Gathered {
+    const uint8_t* payloads;
+    const uint64_t* offs;
+    const uint16_t* lens;
+    const uint32_t* subs;
+    const uint32_t* src_index;
+    uint32_t n_msgs, n_fit;
+    uint64_t n_bytes;
+  };
+
+  // One batch of n <= max_batch slots: pn_udp_classify + pn_udp_gather on the receiver's stream, into device buffers
+  // allocated at the first call; waits for the stream and reads the total back through pinned memory.  `slots` is
+  // read by the GPU where it lies, in either mode: pinned host memory or device memory.  The handler surface's drop
+  // counters are not touched: no record reaches the host.
+  const char* gather(const uint8_t* slots, uint32_t n, Gathered* out) {
+    if (const char* e = gather_begin(n, stride_ - off_, out)) return e;
+    if (n == 0 || subs_.empty()) return nullptr;
+    if (pn_udp_classify(ctx_, slots, stride_, off_, n, g_.res, stream_)) return pn_last_error(ctx_);
+    if (pn_udp_gather(ctx_, slots, stride_, off_, n, g_.res, g_.pay, g_.pay_cap, g_.offs, g_.lens, g_.subs, g_.src,
+                      g_.total, stream_))
+      return pn_last_error(ctx_);
+    return gather_end(out);
+  }
+
+  // The same for frames named by offsets (pn_udp_classify_indexed's contract; `offsets` is any host memory, copied
+  // into a pinned buffer; `ring` pinned host or device memory).  The payload buffer holds max_batch datagrams of
+  // avail - 42 bytes.
+  const char* gatherIndexed(const uint8_t* ring, const uint64_t* offsets, uint32_t n, uint32_t eth_mod16, uint32_t avail,
+                            Gathered* out) {
+    if (avail < 96 || avail > 65536) return "gatherIndexed: avail must be in [96, 65536]";
+    if (const char* e = gather_begin(n, avail, out)) return e;
+    if (n == 0 || subs_.empty()) return nullptr;
+    if (!offsets) return "gatherIndexed: offsets is NULL";
+    std::memcpy(g_.h_offs, offsets, sizeof(uint64_t) * n); // the previous gather has finished: it was waited for
+    if (pn_udp_classify_indexed(ctx_, ring, g_.h_offs, eth_mod16, n, avail, g_.res, stream_)) return pn_last_error(ctx_);
+    if (pn_udp_gather_indexed(ctx_, ring, g_.h_offs, eth_mod16, n, avail, g_.res, g_.pay, g_.pay_cap, g_.offs, g_.lens,
+                              g_.subs, g_.src, g_.total, stream_))
+      return pn_last_error(ctx_);
+    return gather_end(out);
+  }
+
   pn_ctx* ctx() { return ctx_; }
 
  private:
+  // The gather's buffers: device memory but the total and the offsets (pinned).  Owned by this member, so that it
+  // frees them with the receiver; sized for (max_batch, avail) and allocated again when a call needs more.
+  struct GatherBufs {
+    pn_udp_result* res = nullptr;
+    uint8_t* pay = nullptr;
+    uint64_t pay_cap = 0;
+    uint64_t* offs = nullptr;
+    uint16_t* lens = nullptr;
+    uint32_t* subs = nullptr;
+    uint32_t* src = nullptr;
+    uint64_t* h_offs = nullptr;
+    pn_udp_gather_total* total = nullptr;
+    uint32_t batch = 0;
+    GatherBufs() = default;
+    GatherBufs(const GatherBufs&) = delete;
+    GatherBufs& operator=(const GatherBufs&) = delete;
+    ~GatherBufs() { release(); }
+    void release() {
+      if (res) (void)hipFree(res);
+      if (pay) (void)hipFree(pay);
+      if (offs) (void)hipFree(offs);
+      if (lens) (void)hipFree(lens);
+      if (subs) (void)hipFree(subs);
+      if (src) (void)hipFree(src);
+      if (h_offs) (void)hipHostFree(h_offs);
+      if (total) (void)hipHostFree(total);
+      res = nullptr, pay = nullptr, offs = nullptr, lens = nullptr, subs = nullptr, src = nullptr, h_offs = nullptr;
+      total = nullptr;
+      pay_cap = 0, batch = 0;
+    }
+  };
+
+  // Checks, the subscriptions, and buffers for `n` frames of `avail` readable bytes; *out zeroed.
+  const char* gather_begin(uint32_t n, uint32_t avail, Gathered* out) {
+    if (!ctx_) return "gather: init first";
+    if (!out) return "gather: out is NULL";
+    *out = Gathered{};
+    if (n > cap_) return "gather: n must not exceed max_batch";
+    if (n == 0 || subs_.empty()) return nullptr;
+    if (pn_sync(ctx_)) return pn_last_error(ctx_); // nothing is in flight; makes the ctx's device current
+    if (dirty_) { // nothing of this receiver is in flight between calls
+      if (pn_udp_set_subs(ctx_, subs_.data(), (uint32_t)subs_.size())) return pn_last_error(ctx_);
+      dirty_ = false;
+    }
+    const uint64_t want = (uint64_t)cap_ * ((avail - 42 + 15) & ~15u);
+    if (g_.batch != cap_ || g_.pay_cap < want) {
+      g_.release();
+      const size_t b = cap_;
+      if (hipMalloc((void**)&g_.res, sizeof(pn_udp_result) * b) != hipSuccess ||
+          hipMalloc((void**)&g_.pay, want) != hipSuccess || hipMalloc((void**)&g_.offs, sizeof(uint64_t) * b) != hipSuccess ||
+          hipMalloc((void**)&g_.lens, sizeof(uint16_t) * b) != hipSuccess ||
+          hipMalloc((void**)&g_.subs, sizeof(uint32_t) * b) != hipSuccess ||
+          hipMalloc((void**)&g_.src, sizeof(uint32_t) * b) != hipSuccess ||
+          hipHostMalloc((void**)&g_.h_offs, sizeof(uint64_t) * b, hipHostMallocDefault) != hipSuccess ||
+          hipHostMalloc((void**)&g_.total, sizeof(pn_udp_gather_total), hipHostMallocDefault) != hipSuccess) {
+        g_.release();
+        return "gather: allocating the device buffers failed";
+      }
+      g_.pay_cap = want;
+      g_.batch = cap_;
+    }
+    return nullptr;
+  }
+
+  const char* gather_end(Gathered* out) {
+    if (hipStreamSynchronize(stream_) != hipSuccess) return "hipStreamSynchronize failed";
+    out->payloads = g_.pay;
+    out->offs = g_.offs;
+    out->lens = g_.lens;
+    out->subs = g_.subs;
+    out->src_index = g_.src;
+    out->n_msgs = g_.total->n_msgs;
+    out->n_fit = g_.total->n_fit;
+    out->n_bytes = g_.total->n_bytes;
+    return nullptr;
+  }
+
   // EfviUdpReceiver::recvfrom (Efvi.h:251-255): the source address from data - 16, the port from data - 8
   template <class Handler>
   static void deliver_from(Handler& h, uint32_t sub, const uint8_t* data, uint16_t len) {
@@ -269,6 +395,7 @@ class GpuUdpReceiver {
   std::vector<pn_udp_sub> subs_;
   bool dirty_ = false; // subscriptions added since the device table was last set
   uint64_t drop_ip_ = 0, drop_udp_ = 0, drop_len_ = 0;
+  GatherBufs g_; // gather / gatherIndexed only
 };
 
 } // namespace pollnet_amd

@@ -26,6 +26,8 @@ from .rx import (  # noqa: F401
     PN_UDP_MAX_SUBS,
     UDP_CHANNEL_DTYPE,
     PN_UDP_MAX_CHANNELS,
+    UDP_GATHER_TOTAL_DTYPE,
+    PN_UDP_GATHER_ALIGN,
     PN_UB_EFVI,
     PN_UB_PLAIN,
     PN_UB_CSUM,

@@ -51,6 +51,9 @@ struct pn_ctx {
   uint32_t* ub_tbl = nullptr;
   uint32_t ub_cap = 0; // channels allocated
   uint32_t ub_n = 0;   // channels in it (0: none set)
+  void* ug_scratch = nullptr; // pn_udp_gather's per-wave entries (16 B each)
+  uint32_t ug_scratch_n = 0;
+  pn_fence ug;                // the last launch that used ug_scratch
   std::string err;
 };
 
@@ -155,7 +158,7 @@ inline int retire_streams(pn_ctx* ctx) {
   }
   ctx->n_retired = ctx->streams.size();
   ctx->streams.clear();
-  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx}) {
+  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug}) {
     int rc = fence_detach(ctx, *f);
     if (rc) return rc;
   }

@@ -69,17 +69,19 @@ void pn_close(pn_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   // teardown: every launch that may still read ctx memory has finished.  A device-wide wait, so
   // that no stream handle is touched (the caller may have destroyed its streams already)
-  if (ctx->tbl_buf[0] || ctx->tbl_buf[1] || ctx->tx_patch || ctx->sig_count || ctx->udp_tbl || ctx->ub_tbl)
+  if (ctx->tbl_buf[0] || ctx->tbl_buf[1] || ctx->tx_patch || ctx->sig_count || ctx->udp_tbl || ctx->ub_tbl ||
+      ctx->ug_scratch)
     (void)hipDeviceSynchronize();
   for (pn_conn_entry* b : ctx->tbl_buf)
     if (b) (void)hipFree(b);
   if (ctx->udp_tbl) (void)hipFree(ctx->udp_tbl);
   if (ctx->ub_tbl) (void)hipFree(ctx->ub_tbl);
   if (ctx->tx_patch) (void)hipFree(ctx->tx_patch);
+  if (ctx->ug_scratch) (void)hipFree(ctx->ug_scratch);
   if (ctx->sig_count) (void)hipFree(ctx->sig_count);
   for (hipEvent_t ev : ctx->retired)
     if (ev) (void)hipEventDestroy(ev);
-  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx})
+  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug})
     if (f->ev) (void)hipEventDestroy(f->ev);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   delete ctx;
@@ -223,7 +225,7 @@ int pn_sync(pn_ctx* ctx) {
   ctx->streams.clear();
   int rc = pn_internal::wait_retired(ctx);
   if (rc) return rc;
-  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx}) f->state = 0;
+  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug}) f->state = 0;
   return PN_OK;
 }
 

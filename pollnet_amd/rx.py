@@ -72,6 +72,10 @@ PN_UB_EFVI = 0   # ip checksum by Efvi's cached fold (carry defect included), ud
 PN_UB_PLAIN = 1  # ip checksum by CSum::fold, udp checksum 0
 PN_UB_CSUM = 2   # as PLAIN plus the RFC 768 checksum (a computed 0 sent as 0xFFFF)
 assert UDP_CHANNEL_DTYPE.itemsize == 48
+# pn_udp_gather_total: what a gather found (the bytes the messages need, the messages, those that were copied)
+UDP_GATHER_TOTAL_DTYPE = np.dtype([("n_bytes", "<u8"), ("n_msgs", "<u4"), ("n_fit", "<u4")])
+PN_UDP_GATHER_ALIGN = 16
+assert UDP_GATHER_TOTAL_DTYPE.itemsize == 16
 
 
 class UF:
@@ -163,6 +167,9 @@ _pn_udp_classify = _sig("pn_udp_classify", _i32, _vp, _vp, _u32, _u32, _u32, _vp
 _pn_udp_classify_indexed = _sig("pn_udp_classify_indexed", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
 _pn_udp_set_channels = _sig("pn_udp_set_channels", _i32, _vp, _vp, _u32)
 _pn_udp_build = _sig("pn_udp_build", _i32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp)
+_pn_udp_gather = _sig("pn_udp_gather", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp)
+_pn_udp_gather_indexed = _sig("pn_udp_gather_indexed", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp,
+                              _vp, _vp, _vp, _vp)
 _pn_service_open = _sig("pn_service_open", _i32, _vp, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_open_ex = _sig("pn_service_open_ex", _i32, _vp, _u32, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_post = _sig("pn_service_post", _i32, _vp, _vp, _u32, _vp, _vp)
@@ -432,6 +439,33 @@ class RxContext:
                           _ptr(frame_lens), _hold(self, stream)),
             self._h,
             "pn_udp_build",
+        )
+
+    def udp_gather(self, frames, slot_stride: int, frame_off: int, n: int, results, payloads, payload_cap: int,
+                   pay_offs, pay_lens, sub_ids, src_index, total, stream=None):
+        """pn_udp_gather: the payloads of the frames `results` (udp_classify's records for these frames) marks for
+        delivery, packed in frame order into `payloads`, each at a multiple of 16 and zero-padded to one, with
+        udp_build's index arrays: pay_offs u64, pay_lens u16, sub_ids u32 (udp_build's chan_ids), src_index u32 (the
+        frame of each message; None: not written).  total: one UDP_GATHER_TOTAL_DTYPE.  Messages past payload_cap
+        are indexed, not copied.  Buffers in device or pinned memory.  Asynchronous on `stream`."""
+        _check(
+            _pn_udp_gather(self._h, _ptr(frames), slot_stride, frame_off, n, _ptr(results), _ptr(payloads), payload_cap,
+                           _ptr(pay_offs), _ptr(pay_lens), _ptr(sub_ids), None if src_index is None else _ptr(src_index),
+                           _ptr(total), _hold(self, stream)),
+            self._h,
+            "pn_udp_gather",
+        )
+
+    def udp_gather_indexed(self, base, offsets, eth_mod16: int, n: int, avail: int, results, payloads,
+                           payload_cap: int, pay_offs, pay_lens, sub_ids, src_index, total, stream=None):
+        """pn_udp_gather_indexed: udp_gather for frames at base + offsets[i] (udp_classify_indexed's arguments and
+        its records)."""
+        _check(
+            _pn_udp_gather_indexed(self._h, _ptr(base), _ptr(offsets), eth_mod16, n, avail, _ptr(results),
+                                   _ptr(payloads), payload_cap, _ptr(pay_offs), _ptr(pay_lens), _ptr(sub_ids),
+                                   None if src_index is None else _ptr(src_index), _ptr(total), _hold(self, stream)),
+            self._h,
+            "pn_udp_gather_indexed",
         )
 
     def sync(self):

@@ -1,0 +1,25 @@
+"""GPU: GpuUdpReceiver::gather / gatherIndexed (include/pollnet_amd/udp_receiver.hpp) against the handler calls
+poll / pollIndexed make on the same ring (tests/cpp/test_gpu_udp_gather.cpp): the same messages in the same order,
+padded with zeros, from pinned and from device slots; and a relay -- gather, GpuUdpSender::buildDevice with the
+gathered arrays, a second receiver -- through which every payload arrives intact."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "cpp", "test_gpu_udp_gather")
+
+
+@pytest.mark.gpu
+def test_gather_matches_the_handler_calls_and_relays():
+    assert os.path.exists(BIN), "tests/cpp/test_gpu_udp_gather not built (make)"
+    p = subprocess.run([BIN], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "PASS" in p.stdout and "(FAILED)" not in p.stdout, p.stdout
+    for stage in ("gather (pinned slots)", "gather (device slots)", "gather (70 slots from slot 7)",
+                  "gatherIndexed (pinned ring)", "gatherIndexed (device ring)"):
+        assert re.search(re.escape(stage) + r": [1-9]\d* messages", p.stdout), p.stdout
+    m = re.search(r"relay: (\d+) of (\d+) payloads arrived intact", p.stdout)
+    assert m and m.group(1) == m.group(2) and int(m.group(1)) > 60, p.stdout
