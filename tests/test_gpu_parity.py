@@ -283,7 +283,9 @@ def test_long_probe_runs(torch_cuda, ctx, layout):
     """Probe runs far longer than one wave-cooperative pass (the kernel walks a run past
     the home slot 2 entries per lane, then 64 entries per round trip for the whole wave):
     hits at every depth of 300-entry runs, misses that stop on a larger key, runs that end
-    on the EmptyKey sentinel or at the array end, every lane of a wave searching at once."""
+    on the EmptyKey sentinel or at the array end.  At 4,096 frames a wave has eight live lanes
+    (frames_per_wave), and the tables have one home slot or four, so this is the walk at its narrowest:
+    every tier at 8, 16, 32 and 64 lanes, with as many groups as lanes, is tests/test_gpu_probe.py."""
     rng = np.random.default_rng(77)
     keys = sorted({int(k) for k in rng.integers(1, 1 << 48, 420, dtype=np.int64)})[:400]
     ip, port = _key_to_src(keys[5])
@@ -319,7 +321,7 @@ def test_long_probe_runs(torch_cuda, ctx, layout):
             pick.append(absent[int(rng.integers(len(absent)))])
         else:
             pick.append(int(rng.integers(1, 1 << 48)))
-    pick[:64] = [present[-1 - j] for j in range(64)]  # one wave whose 64 lanes all walk deep
+    pick[:64] = [present[-1 - j] for j in range(64)]  # eight waves whose eight live lanes all walk deep
     frames = []
     for k in pick:
         ip, port = _key_to_src(k)
