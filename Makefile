@@ -8,14 +8,14 @@ CFLAGS_ORACLE = -O3 -march=x86-64-v3 -fPIC -Wall -std=c11
 LIB = pollnet_amd/libpollnet_amd.so
 SRCS = pollnet_amd/csrc/rx_kernel.hip pollnet_amd/csrc/rx_service.hip pollnet_amd/csrc/stream_kernel.hip pollnet_amd/csrc/tx_kernel.hip \
   pollnet_amd/csrc/udp_kernel.hip pollnet_amd/csrc/udp_indexed_kernel.hip pollnet_amd/csrc/udp_build_kernel.hip \
-  pollnet_amd/csrc/udp_gather_kernel.hip pollnet_amd/csrc/conn_table.cpp
+  pollnet_amd/csrc/udp_gather_kernel.hip pollnet_amd/csrc/udp_demux_kernel.hip pollnet_amd/csrc/conn_table.cpp
 # the seeded workload generator (tests, bench): its own library, outside the product ABI
 GEN_LIB = pollnet_amd/libpollnet_amd_gen.so
 HDRS = include/pollnet_amd.h
 KHDRS = pollnet_amd/csrc/frame_pass.hpp pollnet_amd/csrc/device_common.hpp pollnet_amd/csrc/pn_internal.hpp \
   pollnet_amd/csrc/rx_classify.hpp pollnet_amd/csrc/tx_fill.hpp pollnet_amd/csrc/stream_match.hpp \
   pollnet_amd/csrc/udp_classify.hpp pollnet_amd/csrc/udp_indexed.hpp pollnet_amd/csrc/udp_build.hpp \
-  pollnet_amd/csrc/udp_gather.hpp
+  pollnet_amd/csrc/udp_gather.hpp pollnet_amd/csrc/udp_demux.hpp
 # measurement-only library (bench ceilings, match-streams variants, test helpers): never loaded by the product
 TUNING_LIB = pollnet_amd/libpollnet_amd_tuning.so
 TUNING_SRCS = pollnet_amd/csrc/rx_tuning.hip pollnet_amd/csrc/tx_tuning.hip
@@ -53,6 +53,8 @@ UDPTMPLTEST = tests/cpp/test_udp_sender_template
 UDPTXBENCH = bench/bench_udp_tx
 UDPGATHERTEST = tests/cpp/test_gpu_udp_gather
 UDPGATHERBENCH = bench/bench_udp_gather
+UDPDEMUXTEST = tests/cpp/test_gpu_udp_demux
+UDPDEMUXBENCH = bench/bench_udp_demux
 
 # Host programs that include HIP headers: compiled by hipcc with the device pass pinned to gfx950
 # (without --offload-arch hipcc would add a default-arch device pass for nothing)
@@ -70,7 +72,7 @@ CONN_INCS = $(addprefix oracle/_ref/,conn_tcpconn.inc conn_tcpserver.inc conn_ef
 HAVE_REF_TEXT = $(or $(wildcard $(REFDIR)/example/tcpserver.cc),$(and $(wildcard oracle/_ref/tcpserver_handler.inc),$(wildcard oracle/_ref/tcpclient_handler.inc)))
 REF_TESTS = $(if $(HAVE_REF_TEXT),$(SERVERTEST) $(CLISRVTEST) $(REFSERVERTEST) $(REFCONNTEST) $(REFCLIENTTEST))
 
-all: $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) ref $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(REF_TESTS) $(PEERTEST) $(TXHOSTTEST) $(UDPRXTEST) $(UDPRXBENCH) $(UDPRXIDXTEST) $(UDPLAYOUTTEST) $(UDPTXTEST) $(UDPTMPLTEST) $(UDPTXBENCH) $(UDPGATHERTEST) $(UDPGATHERBENCH)
+all: $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) ref $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(REF_TESTS) $(PEERTEST) $(TXHOSTTEST) $(UDPRXTEST) $(UDPRXBENCH) $(UDPRXIDXTEST) $(UDPLAYOUTTEST) $(UDPTXTEST) $(UDPTMPLTEST) $(UDPTXBENCH) $(UDPGATHERTEST) $(UDPGATHERBENCH) $(UDPDEMUXTEST) $(UDPDEMUXBENCH)
 
 # GpuUdpSender (flush, buildDevice, the ring's wrap) vs a sequential twin of EfviUdpSender::init + write, then the
 # built ring through a GpuUdpReceiver (GPU)
@@ -83,6 +85,17 @@ $(UDPTXTEST): tests/cpp/test_gpu_udp_tx.cpp include/pollnet_amd/udp_sender.hpp i
 $(UDPGATHERTEST): tests/cpp/test_gpu_udp_gather.cpp include/pollnet_amd/udp_sender.hpp include/pollnet_amd/udp_receiver.hpp \
   include/pollnet_amd/gpu_rx.hpp $(HDRS) $(LIB)
 	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -Wl,-rpath,'$$ORIGIN/../../pollnet_amd'
+
+# GpuUdpReceiver::gatherBySub / gatherBySubIndexed vs the handler calls of poll / pollIndexed on the same ring bucketed
+# per subscription, and a relay: gatherBySub -> GpuUdpSender::buildDevice -> a second receiver (GPU)
+$(UDPDEMUXTEST): tests/cpp/test_gpu_udp_demux.cpp include/pollnet_amd/udp_sender.hpp include/pollnet_amd/udp_receiver.hpp \
+  include/pollnet_amd/gpu_rx.hpp $(HDRS) $(LIB)
+	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -Wl,-rpath,'$$ORIGIN/../../pollnet_amd'
+
+# pn_udp_demux on device-resident slots: 1,024 / 1 / 4,096 subscriptions, 64-B datagrams, 1 in 16 taken, each vs
+# pn_udp_gather on the same ring, one run
+$(UDPDEMUXBENCH): bench/bench_udp_demux.cpp $(HDRS) $(LIB)
+	$(HOSTHIP) -O2 -std=c++17 -Wall -o $@ $< -Lpollnet_amd -lpollnet_amd -Wl,-rpath,'$$ORIGIN/../pollnet_amd'
 
 # pn_udp_gather on device-resident slots: 1472-B and 64-B datagrams, classify + gather, 1 in 16 taken, vs
 # pn_udp_classify, pn_udp_build of the same messages and a device copy of the same bytes, one run
@@ -252,7 +265,7 @@ ref:
 	@if [ -d $(REFDIR) ]; then $(MAKE) -C oracle -f ref.mk REFDIR=$(REFDIR); else echo "no $(REFDIR): using prebuilt oracle/_ref"; fi
 
 clean:
-	rm -f $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) oracle/_ref/*.so $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(SERVERTEST) $(PEERTEST) $(CLISRVTEST) $(TXHOSTTEST) $(REFSERVERTEST) $(REFCONNTEST) $(REFCLIENTTEST) $(UDPRXTEST) $(UDPRXBENCH) $(UDPRXIDXTEST) $(UDPLAYOUTTEST) $(UDPTXTEST) $(UDPTMPLTEST) $(UDPTXBENCH) $(UDPGATHERTEST) $(UDPGATHERBENCH)
+	rm -f $(LIB) $(GEN_LIB) $(TUNING_LIB) $(ORACLE) oracle/_ref/*.so $(CPPTEST) $(RXCONNTEST) $(TCPRXTEST) $(TCPRXBENCH) $(LATBENCH) $(SRVBENCH) $(PINBENCH) $(SIGBENCH) $(STREAMBENCH) $(DOORBENCH) $(RINGTEST) $(STREAMTEST) $(GPUSTREAMTEST) $(SERVERTEST) $(PEERTEST) $(CLISRVTEST) $(TXHOSTTEST) $(REFSERVERTEST) $(REFCONNTEST) $(REFCLIENTTEST) $(UDPRXTEST) $(UDPRXBENCH) $(UDPRXIDXTEST) $(UDPLAYOUTTEST) $(UDPTXTEST) $(UDPTMPLTEST) $(UDPTXBENCH) $(UDPGATHERTEST) $(UDPGATHERBENCH) $(UDPDEMUXTEST) $(UDPDEMUXBENCH)
 
 .PHONY: all ref clean svc_trace
 

@@ -384,6 +384,53 @@ int pn_udp_gather_indexed(pn_ctx* ctx, const void* base, const uint64_t* offsets
                           uint64_t* pay_offs, uint16_t* pay_lens, uint32_t* sub_ids, uint32_t* src_index,
                           pn_udp_gather_total* total, void* stream);
 
+/* ---- UDP demux: the delivered payloads of a classified ring grouped by subscription ----
+ * What a set of EfviUdpReceiver objects gives for free (each sees only its own filter's datagrams, Efvi.h:194-207),
+ * for a whole batch and for a consumer on the GPU: pn_udp_gather's output, stably sorted by subscription, so that each
+ * subscription owns one contiguous run of messages and of bytes, in arrival order.
+ *
+ * The layout, alignment and memory-kind contracts are pn_udp_gather's and pn_udp_gather_indexed's, the dword-granular
+ *   read rule of the indexed call and "no byte of a frame that is not taken is read" included.  n_subs is in
+ *   [1, PN_UDP_MAX_SUBS]; sub_first (4-byte aligned) and sub_bytes (8-byte aligned) hold n_subs + 1 entries each and
+ *   may not be NULL, even when n == 0; n <= PN_UDP_DEMUX_MAX_N.  Needs no subscription table.
+ * Frame i is taken iff pn_udp_gather would take it and results[i].sub_id < n_subs: a forged or stale record with a
+ *   larger id is skipped, it indexes nothing.
+ * The taken frames, stably sorted by (sub_id, i), are messages 0 .. n_msgs-1.  For message j: pay_lens[j], sub_ids[j]
+ *   and src_index[j] = i (src_index may be NULL) are written; pay_offs[j] = the sum of round_up(len_k, 16) over k < j in
+ *   this grouped order; its bytes are copied from eth + 42 to payloads + pay_offs[j] and the pad is written as zero.
+ * sub_first[s] = the number of messages with sub_id < s and sub_first[n_subs] = n_msgs; sub_bytes[s] = the byte offset
+ *   where subscription s's messages start and sub_bytes[n_subs] = n_bytes: subscription s owns messages
+ *   [sub_first[s], sub_first[s+1]) and bytes [sub_bytes[s], sub_bytes[s+1]), both empty when it received nothing.
+ *   All n_subs + 1 entries of both are always written.
+ * total: n_msgs and n_bytes as pn_udp_gather reports them for the same taken set; n_fit = the leading messages in
+ *   grouped order that end at or below payload_cap.  Offsets ascend, so the copied messages are a prefix; a message
+ *   that does not fit is indexed but not copied.
+ * Nothing else is written: entries j >= n_msgs of the four per-message arrays, everything after entry n_subs of the
+ *   per-subscription arrays, the payload bytes past the last copied message, the frames and the records keep their
+ *   value.  No value in results, in offsets or in the call's own scratch makes a kernel read outside [eth, eth + avail)
+ *   of a taken frame or write outside [payloads, payloads + payload_cap), the first n entries of the per-message
+ *   arrays, the first n_subs + 1 entries of the per-subscription arrays and total: the copy re-checks each message
+ *   against payload_cap with the offset it computed itself, repeats the taken test on the record it reads and clamps
+ *   every index it takes from scratch.  Records that change between the call's launches can garble the output, not
+ *   escape it.
+ * n == 0 returns PN_OK with total zeroed and both per-subscription arrays zero-filled on the stream, nothing else
+ *   written.  A NULL or misaligned pointer, n_subs or n out of range, or a broken layout contract: PN_EINVAL.
+ * Asynchronous on `stream` (eight launches; scratch owned by the ctx, a call on another stream than the previous one
+ *   is ordered after it on the device).  The output is a function of the inputs alone: no atomic decides a message's
+ *   position and no workgroup waits for another.
+ * With (L, S, I) pn_udp_gather's pay_lens, sub_ids and src_index for the same inputs restricted to S < n_subs and pi
+ *   the stable argsort of S: pay_lens, sub_ids, src_index = L[pi], S[pi], I[pi]; pay_offs = the exclusive running sum
+ *   of round_up(L[pi], 16); every copied message holds the bytes the gather copies. */
+#define PN_UDP_DEMUX_MAX_N (1u << 24)
+int pn_udp_demux(pn_ctx* ctx, const void* frames, uint32_t slot_stride, uint32_t frame_off, uint32_t n,
+                 const void* results, uint32_t n_subs, void* payloads, uint64_t payload_cap, uint64_t* pay_offs,
+                 uint16_t* pay_lens, uint32_t* sub_ids, uint32_t* src_index, uint32_t* sub_first, uint64_t* sub_bytes,
+                 pn_udp_gather_total* total, void* stream);
+int pn_udp_demux_indexed(pn_ctx* ctx, const void* base, const uint64_t* offsets, uint32_t eth_mod16, uint32_t n,
+                         uint32_t avail, const void* results, uint32_t n_subs, void* payloads, uint64_t payload_cap,
+                         uint64_t* pay_offs, uint16_t* pay_lens, uint32_t* sub_ids, uint32_t* src_index,
+                         uint32_t* sub_first, uint64_t* sub_bytes, pn_udp_gather_total* total, void* stream);
+
 /* ---- TX checksum fill over a batch of outgoing frames ----
  * Replaces the reference's per-frame checksum finalisation on the send side:
  *   PN_TX_TCP      efvitcp: SendBuf::setOptDataLen (Core.h:157-163) at the end of

@@ -19,6 +19,8 @@
 // gather / gatherIndexed are poll / pollIndexed for a consumer on the GPU: instead of one handler call per datagram,
 // the delivered payloads of one batch packed in order into a device buffer, with the index arrays
 // GpuUdpSender::buildDevice (pn_udp_build) takes (pn_udp_gather).
+// gatherBySub / gatherBySubIndexed are the same grouped by subscription (pn_udp_demux): each subscription's messages
+// contiguous and in arrival order, as each of the reference's receiver objects sees only its own filter's datagrams.
 // Errors follow the reference: const char* (nullptr = ok).
 #pragma once
 
@@ -176,6 +178,45 @@ class GpuUdpReceiver {
     return gather_end(out);
   }
 
+  // What a gatherBySub leaves on the device: Gathered's fields with the messages stably sorted by subscription, and
+  // sub_first / sub_bytes (subCount() + 1 entries each): subscription s owns messages [sub_first[s], sub_first[s+1])
+  // and bytes [sub_bytes[s], sub_bytes[s+1]) of payloads.  With n == 0 or no subscription every field is zero.
+  struct GatheredBySub : Gathered {
+    const uint32_t* sub_first;
+    const uint64_t* sub_bytes;
+  };
+
+  // gather with the output grouped by subscription: pn_udp_classify + pn_udp_demux on the receiver's stream, n_subs =
+  // the receiver's own subscription count.  The drop counters are not touched.
+  const char* gatherBySub(const uint8_t* slots, uint32_t n, GatheredBySub* out) {
+    if (!out) return "gatherBySub: out is NULL";
+    *out = GatheredBySub{};
+    if (const char* e = gather_begin(n, stride_ - off_, out)) return e;
+    if (n == 0 || subs_.empty()) return nullptr;
+    if (pn_udp_classify(ctx_, slots, stride_, off_, n, g_.res, stream_)) return pn_last_error(ctx_);
+    if (pn_udp_demux(ctx_, slots, stride_, off_, n, g_.res, (uint32_t)subs_.size(), g_.pay, g_.pay_cap, g_.offs, g_.lens,
+                     g_.subs, g_.src, g_.sub_first, g_.sub_bytes, g_.total, stream_))
+      return pn_last_error(ctx_);
+    return by_sub_end(out);
+  }
+
+  // gatherIndexed with the output grouped by subscription (pn_udp_classify_indexed + pn_udp_demux_indexed).
+  const char* gatherBySubIndexed(const uint8_t* ring, const uint64_t* offsets, uint32_t n, uint32_t eth_mod16,
+                                 uint32_t avail, GatheredBySub* out) {
+    if (!out) return "gatherBySubIndexed: out is NULL";
+    *out = GatheredBySub{};
+    if (avail < 96 || avail > 65536) return "gatherBySubIndexed: avail must be in [96, 65536]";
+    if (const char* e = gather_begin(n, avail, out)) return e;
+    if (n == 0 || subs_.empty()) return nullptr;
+    if (!offsets) return "gatherBySubIndexed: offsets is NULL";
+    std::memcpy(g_.h_offs, offsets, sizeof(uint64_t) * n); // the previous gather has finished: it was waited for
+    if (pn_udp_classify_indexed(ctx_, ring, g_.h_offs, eth_mod16, n, avail, g_.res, stream_)) return pn_last_error(ctx_);
+    if (pn_udp_demux_indexed(ctx_, ring, g_.h_offs, eth_mod16, n, avail, g_.res, (uint32_t)subs_.size(), g_.pay,
+                             g_.pay_cap, g_.offs, g_.lens, g_.subs, g_.src, g_.sub_first, g_.sub_bytes, g_.total, stream_))
+      return pn_last_error(ctx_);
+    return by_sub_end(out);
+  }
+
   pn_ctx* ctx() { return ctx_; }
 
  private:
@@ -189,6 +230,8 @@ class GpuUdpReceiver {
     uint16_t* lens = nullptr;
     uint32_t* subs = nullptr;
     uint32_t* src = nullptr;
+    uint32_t* sub_first = nullptr; // gatherBySub: PN_UDP_MAX_SUBS + 1 entries each
+    uint64_t* sub_bytes = nullptr;
     uint64_t* h_offs = nullptr;
     pn_udp_gather_total* total = nullptr;
     uint32_t batch = 0;
@@ -203,10 +246,12 @@ class GpuUdpReceiver {
       if (lens) (void)hipFree(lens);
       if (subs) (void)hipFree(subs);
       if (src) (void)hipFree(src);
+      if (sub_first) (void)hipFree(sub_first);
+      if (sub_bytes) (void)hipFree(sub_bytes);
       if (h_offs) (void)hipHostFree(h_offs);
       if (total) (void)hipHostFree(total);
       res = nullptr, pay = nullptr, offs = nullptr, lens = nullptr, subs = nullptr, src = nullptr, h_offs = nullptr;
-      total = nullptr;
+      total = nullptr, sub_first = nullptr, sub_bytes = nullptr;
       pay_cap = 0, batch = 0;
     }
   };
@@ -232,6 +277,8 @@ class GpuUdpReceiver {
           hipMalloc((void**)&g_.lens, sizeof(uint16_t) * b) != hipSuccess ||
           hipMalloc((void**)&g_.subs, sizeof(uint32_t) * b) != hipSuccess ||
           hipMalloc((void**)&g_.src, sizeof(uint32_t) * b) != hipSuccess ||
+          hipMalloc((void**)&g_.sub_first, sizeof(uint32_t) * (PN_UDP_MAX_SUBS + 1)) != hipSuccess ||
+          hipMalloc((void**)&g_.sub_bytes, sizeof(uint64_t) * (PN_UDP_MAX_SUBS + 1)) != hipSuccess ||
           hipHostMalloc((void**)&g_.h_offs, sizeof(uint64_t) * b, hipHostMallocDefault) != hipSuccess ||
           hipHostMalloc((void**)&g_.total, sizeof(pn_udp_gather_total), hipHostMallocDefault) != hipSuccess) {
         g_.release();
@@ -253,6 +300,13 @@ class GpuUdpReceiver {
     out->n_msgs = g_.total->n_msgs;
     out->n_fit = g_.total->n_fit;
     out->n_bytes = g_.total->n_bytes;
+    return nullptr;
+  }
+
+  const char* by_sub_end(GatheredBySub* out) {
+    if (const char* e = gather_end(out)) return e;
+    out->sub_first = g_.sub_first;
+    out->sub_bytes = g_.sub_bytes;
     return nullptr;
   }
 

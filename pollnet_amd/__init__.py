@@ -28,6 +28,7 @@ from .rx import (  # noqa: F401
     PN_UDP_MAX_CHANNELS,
     UDP_GATHER_TOTAL_DTYPE,
     PN_UDP_GATHER_ALIGN,
+    PN_UDP_DEMUX_MAX_N,
     PN_UB_EFVI,
     PN_UB_PLAIN,
     PN_UB_CSUM,

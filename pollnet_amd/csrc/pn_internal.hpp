@@ -54,6 +54,9 @@ struct pn_ctx {
   void* ug_scratch = nullptr; // pn_udp_gather's per-wave entries (16 B each)
   uint32_t ug_scratch_n = 0;
   pn_fence ug;                // the last launch that used ug_scratch
+  void* ud_scratch = nullptr; // pn_udp_demux's count matrix, source indices and scan entries (udp_demux.hpp)
+  size_t ud_scratch_bytes = 0;
+  pn_fence ud;                // the last launch that used ud_scratch
   std::string err;
 };
 
@@ -158,7 +161,7 @@ inline int retire_streams(pn_ctx* ctx) {
   }
   ctx->n_retired = ctx->streams.size();
   ctx->streams.clear();
-  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug}) {
+  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug, &ctx->ud}) {
     int rc = fence_detach(ctx, *f);
     if (rc) return rc;
   }

@@ -70,7 +70,7 @@ void pn_close(pn_ctx* ctx) {
   // teardown: every launch that may still read ctx memory has finished.  A device-wide wait, so
   // that no stream handle is touched (the caller may have destroyed its streams already)
   if (ctx->tbl_buf[0] || ctx->tbl_buf[1] || ctx->tx_patch || ctx->sig_count || ctx->udp_tbl || ctx->ub_tbl ||
-      ctx->ug_scratch)
+      ctx->ug_scratch || ctx->ud_scratch)
     (void)hipDeviceSynchronize();
   for (pn_conn_entry* b : ctx->tbl_buf)
     if (b) (void)hipFree(b);
@@ -78,10 +78,11 @@ void pn_close(pn_ctx* ctx) {
   if (ctx->ub_tbl) (void)hipFree(ctx->ub_tbl);
   if (ctx->tx_patch) (void)hipFree(ctx->tx_patch);
   if (ctx->ug_scratch) (void)hipFree(ctx->ug_scratch);
+  if (ctx->ud_scratch) (void)hipFree(ctx->ud_scratch);
   if (ctx->sig_count) (void)hipFree(ctx->sig_count);
   for (hipEvent_t ev : ctx->retired)
     if (ev) (void)hipEventDestroy(ev);
-  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug})
+  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug, &ctx->ud})
     if (f->ev) (void)hipEventDestroy(f->ev);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   delete ctx;
@@ -225,7 +226,7 @@ int pn_sync(pn_ctx* ctx) {
   ctx->streams.clear();
   int rc = pn_internal::wait_retired(ctx);
   if (rc) return rc;
-  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug}) f->state = 0;
+  for (pn_fence* f : {&ctx->sig[0], &ctx->sig[1], &ctx->tx, &ctx->ug, &ctx->ud}) f->state = 0;
   return PN_OK;
 }
 

@@ -75,6 +75,7 @@ assert UDP_CHANNEL_DTYPE.itemsize == 48
 # pn_udp_gather_total: what a gather found (the bytes the messages need, the messages, those that were copied)
 UDP_GATHER_TOTAL_DTYPE = np.dtype([("n_bytes", "<u8"), ("n_msgs", "<u4"), ("n_fit", "<u4")])
 PN_UDP_GATHER_ALIGN = 16
+PN_UDP_DEMUX_MAX_N = 1 << 24
 assert UDP_GATHER_TOTAL_DTYPE.itemsize == 16
 
 
@@ -170,6 +171,10 @@ _pn_udp_build = _sig("pn_udp_build", _i32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _
 _pn_udp_gather = _sig("pn_udp_gather", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp)
 _pn_udp_gather_indexed = _sig("pn_udp_gather_indexed", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp,
                               _vp, _vp, _vp, _vp)
+_pn_udp_demux = _sig("pn_udp_demux", _i32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
+                     _vp, _vp)
+_pn_udp_demux_indexed = _sig("pn_udp_demux_indexed", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u64, _vp,
+                             _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 _pn_service_open = _sig("pn_service_open", _i32, _vp, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_open_ex = _sig("pn_service_open_ex", _i32, _vp, _u32, _u32, _u32, _u32, _c.POINTER(_vp))
 _pn_service_post = _sig("pn_service_post", _i32, _vp, _vp, _u32, _vp, _vp)
@@ -466,6 +471,36 @@ class RxContext:
                                    None if src_index is None else _ptr(src_index), _ptr(total), _hold(self, stream)),
             self._h,
             "pn_udp_gather_indexed",
+        )
+
+    def udp_demux(self, frames, slot_stride: int, frame_off: int, n: int, results, n_subs: int, payloads,
+                  payload_cap: int, pay_offs, pay_lens, sub_ids, src_index, sub_first, sub_bytes, total, stream=None):
+        """pn_udp_demux: udp_gather's output grouped by subscription -- the taken frames with sub_id < n_subs stably
+        sorted by (sub_id, frame), so each subscription's messages are contiguous and in arrival order.  The arrays
+        of udp_gather in that order, plus sub_first u32 and sub_bytes u64 of n_subs + 1 entries each: subscription s
+        owns messages [sub_first[s], sub_first[s+1]) and bytes [sub_bytes[s], sub_bytes[s+1]).  total: one
+        UDP_GATHER_TOTAL_DTYPE.  Buffers in device or pinned memory.  Asynchronous on `stream`."""
+        _check(
+            _pn_udp_demux(self._h, _ptr(frames), slot_stride, frame_off, n, _ptr(results), n_subs, _ptr(payloads),
+                          payload_cap, _ptr(pay_offs), _ptr(pay_lens), _ptr(sub_ids),
+                          None if src_index is None else _ptr(src_index), _ptr(sub_first), _ptr(sub_bytes), _ptr(total),
+                          _hold(self, stream)),
+            self._h,
+            "pn_udp_demux",
+        )
+
+    def udp_demux_indexed(self, base, offsets, eth_mod16: int, n: int, avail: int, results, n_subs: int, payloads,
+                          payload_cap: int, pay_offs, pay_lens, sub_ids, src_index, sub_first, sub_bytes, total,
+                          stream=None):
+        """pn_udp_demux_indexed: udp_demux for frames at base + offsets[i] (udp_classify_indexed's arguments and its
+        records)."""
+        _check(
+            _pn_udp_demux_indexed(self._h, _ptr(base), _ptr(offsets), eth_mod16, n, avail, _ptr(results), n_subs,
+                                  _ptr(payloads), payload_cap, _ptr(pay_offs), _ptr(pay_lens), _ptr(sub_ids),
+                                  None if src_index is None else _ptr(src_index), _ptr(sub_first), _ptr(sub_bytes),
+                                  _ptr(total), _hold(self, stream)),
+            self._h,
+            "pn_udp_demux_indexed",
         )
 
     def sync(self):
